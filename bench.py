@@ -2,8 +2,15 @@
 20M-row synthetic Vlasov operator (BASELINE.json configs[3], the north_star's target), one
 rank per MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K solves and prints the headline line (value,
+ms_per_step, iterations, info).  --dump-outputs DIR also writes the last timed solve's x and
+info as DIR/*.npy (dump_outputs below).  --full adds everything that takes runs of its own: the
+true residual, the SpMV / copy / read bandwidth probes, the per-kernel profile with `roofline`
+and the SURVEY 8(d) reconciliation, the line-preconditioner solve and `cpu_baseline`.
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) the script starts its own N ranks: the
 parent process never touches the GPU, it spawns N fresh children (RANK / LOCAL_RANK /
@@ -17,7 +24,7 @@ contiguous x-slabs, RCCL halo exchange + all-reduce).  Operator, RHS and BJ inve
 on the device before the timed region; b and x live in HBM (torch tensors passed through the
 C-ABI as device pointers).
 
-Printed: ONE JSON line on rank 0 (the driver's contract), with `roofline` (the dominant
+Printed: ONE JSON line on rank 0 (the driver's contract); with --full it holds `roofline` (the dominant
 kernel, timed live with HIP events on the context's stream) and `cpu_baseline` (SciPy, the
 north_star's reference scipy.sparse path: one full solve of the same operator and RHS to the
 same tolerance on the box's host cores; --cpu-sample bounds it to the first --cpu-inner inner
@@ -124,6 +131,25 @@ def cpu_baseline(cfg_name, A_host, b, bs, rtol, inner_limit, line=None, full=Tru
     return out
 
 
+DUMP_SAMPLE = 1 << 21   # entries of x written by --dump-outputs when x is longer (16 MB of float64)
+
+
+def dump_outputs(dirname, x, info, rank, world):
+    """--dump-outputs: what vtkrylov.gmres returned in the last timed solve, as float64 .npy files.
+    `x` whole up to DUMP_SAMPLE entries, else its entries at DUMP_SAMPLE sorted positions drawn
+    with a fixed seed (the same positions in every run of the same arguments); `info` as a
+    one-element array.  With several ranks each writes its own rows (`x_rank<r>.npy`)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    xh = x.detach().cpu().numpy().astype(np.float64, copy=False)
+    if xh.shape[0] > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0x5EED + rank).integers(0, xh.shape[0], DUMP_SAMPLE))
+        xh = xh[pos]
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"x{tag}.npy"), np.ascontiguousarray(xh))
+    np.save(os.path.join(dirname, f"info{tag}.npy"), np.array([info], dtype=np.float64))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -172,7 +198,13 @@ def main():
     ap.add_argument("--rtol", type=float, default=1e-8)
     ap.add_argument("--restart", type=int, default=20)
     ap.add_argument("--spmv-reps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed solves also run every other check and measurement: true residual, "
+                         "SpMV / copy / read bandwidth probes, the per-kernel profile and roofline, the "
+                         "line-preconditioner solve and the SciPy CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (x, info) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the SciPy baseline")
     ap.add_argument("--cpu-inner", type=int, default=20,
                     help="with --cpu-sample: inner iterations of the bounded SciPy sample")
     ap.add_argument("--cpu-sample", action="store_true",
@@ -206,6 +238,8 @@ def main():
                          "rank 0 prints one JSON line")
     ap.add_argument("--check-launch-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the metric is measured over the timed solves)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))   # no GPU call has happened in this process
 
@@ -327,6 +361,52 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    ms = elapsed / args.steps * 1e3
+    # the headline: everything the timed solves alone determine
+    head = {
+        "metric": "precond-GMRES iters/sec + CSR SpMV achieved-HBM-GB/s, 1/2/4/8 MI355X",
+        "value": iters / elapsed,
+        "unit": "iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64" if not fp32 else "f32-values/f64",
+        "data": "synthetic (SURVEY.md Appendix A Vlasov operator, splitmix64 RHS), " +
+                {"generated": "generated on device", "upload": "uploaded as a host CSR (vtkrylov.csr_matrix)",
+                 "npz": "read from a save_npz archive (vtkrylov.load_npz)"}[args.operator],
+        "config": {"workload": f"{args.config}{'/' + str(args.slab) + ' slab' if args.slab > 1 else ''}: "
+                               f"GMRES({args.restart}, {args.orth})+{mdesc} to rtol={args.rtol}, "
+                               f"n={n_glob}, row-sharded over {world} GPU(s)",
+                   "n": n_glob, "nnz": int(params_nnz(dim, shape)), "restart": args.restart,
+                   "prec": args.prec, "bs": args.bs if args.prec == "bj" else None, "operator": args.operator,
+                   "line_band": A.line_band, "line_values": A.line_values,
+                   "seg": args.seg if args.prec == "line" else None, "bj_apply": mmode, "layout": A.layout,
+                   "rtol": args.rtol, "orth": args.orth,
+                   "parallelism": f"row-slab x{world}",
+                   "comm": args.comm if world > 1 else ("rccl-solo" if args.comm_solo else None),
+                   "launcher": ("bench.py" if os.environ.get("VTK_BENCH_SPAWNED") else "external") if world > 1 else None},
+        "rccl_ranks": ctx.rccl_ranks(),
+        "build_id": build_id,
+        "inner_iters_per_solve": iters / args.steps,
+        "solves_per_s": args.steps / elapsed,
+        "solve_ms_median": sorted(per_solve)[len(per_solve) // 2] * 1e3,
+        "info": infos,
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, info, rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- everything below is --full only: checks and measurements that take runs of their own
     # true residual of the last solve, on the device (vtk_spmv), reduced over ranks
     r = b - A @ x
     rn2 = torch.tensor([float(torch.dot(r, r).item()), float(torch.dot(b, b).item())], dtype=torch.float64)
@@ -440,7 +520,6 @@ def main():
                                "launches": v["launches"], "share": round(v["seconds"] / tot_l, 4)}
                            for k, v in sorted(kprof_l.items(), key=lambda kv: -kv[1]["seconds"])}}
 
-    ms = elapsed / args.steps * 1e3
     # ---- reconciliation with SURVEY §8(d)'s byte model (MGS, inverse BJ(bs), CSR int32 columns):
     # (1) the dominant kernel with its SELL matrix bytes replaced by CSR's (same algorithm,
     #     §8(d)'s matrix encoding); (2) the whole solve's actual algorithmic bytes (every
@@ -486,36 +565,7 @@ def main():
                               "note": "MGS + inverse BJ + CSR int32 byte model of 8(d) / ms_per_step"},
     }
     out = {
-        "metric": "precond-GMRES iters/sec + CSR SpMV achieved-HBM-GB/s, 1/2/4/8 MI355X",
-        "value": iters / elapsed,
-        "unit": "iters/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64" if not fp32 else "f32-values/f64",
-        "data": "synthetic (SURVEY.md Appendix A Vlasov operator, splitmix64 RHS), " +
-                {"generated": "generated on device", "upload": "uploaded as a host CSR (vtkrylov.csr_matrix)",
-                 "npz": "read from a save_npz archive (vtkrylov.load_npz)"}[args.operator],
-        "config": {"workload": f"{args.config}{'/' + str(args.slab) + ' slab' if args.slab > 1 else ''}: "
-                               f"GMRES({args.restart}, {args.orth})+{mdesc} to rtol={args.rtol}, "
-                               f"n={n_glob}, row-sharded over {world} GPU(s)",
-                   "n": n_glob, "nnz": int(params_nnz(dim, shape)), "restart": args.restart,
-                   "prec": args.prec, "bs": args.bs if args.prec == "bj" else None, "operator": args.operator,
-                   "line_band": A.line_band, "line_values": A.line_values,
-                   "seg": args.seg if args.prec == "line" else None, "bj_apply": mmode, "layout": A.layout, "rtol": args.rtol, "orth": args.orth,
-                   "parallelism": f"row-slab x{world}",
-                   "comm": args.comm if world > 1 else ("rccl-solo" if args.comm_solo else None),
-                   "launcher": ("bench.py" if os.environ.get("VTK_BENCH_SPAWNED") else "external") if world > 1 else None},
-        "rccl_ranks": ctx.rccl_ranks(),
-        "build_id": build_id,
-        "inner_iters_per_solve": iters / args.steps,
-        "solves_per_s": args.steps / elapsed,
-        "solve_ms_median": sorted(per_solve)[len(per_solve) // 2] * 1e3,
-        "info": infos,
+        **head,
         "true_rel_residual": rel_res,
         "spmv": {"gbs": spmv_gbs, "hbm_frac": spmv_gbs / HBM_PEAK_GBS, "us": t_spmv * 1e6, "bytes": B,
                  "layout": linfo["layout"], "wide_chunks": linfo["wide_chunks"],

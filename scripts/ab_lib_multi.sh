@@ -10,7 +10,7 @@ while IFS= read -r cfg; do
   for r in 1 2; do
     for v in new old; do
       if [ $v = old ]; then export VTK_LIB=$PWD/ablib/libvtkrylov_old.so; else unset VTK_LIB; fi
-      timeout -k 10 300 python bench.py $cfg --no-cpu-baseline > $O/b${i}_${v}_$r.log 2>&1
+      timeout -k 10 300 python bench.py --full $cfg --no-cpu-baseline > $O/b${i}_${v}_$r.log 2>&1
       grep '^{' $O/b${i}_${v}_$r.log | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$i', '$cfg', '$v', $r, round(d['value'],1))"
     done
   done

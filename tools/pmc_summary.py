@@ -99,7 +99,7 @@ def main():
     ap.add_argument("--prof", default="prof")
     ap.add_argument("--fetch", default="pmc_fetch")
     ap.add_argument("--write", default="pmc_write")
-    ap.add_argument("--cmd", default="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --spmv-reps 5")
+    ap.add_argument("--cmd", default="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --spmv-reps 5")
     ap.add_argument("--config", default="C3", help="bench config the profiled command ran (bench.py matches it)")
     ap.add_argument("--sq", default=None, help="dir of a --pmc SQ_* pass: per-kernel mean counters -> <tag>pmc_sq.json")
     ap.add_argument("--patch-bench", default=None,
