@@ -216,6 +216,31 @@ int vtk_csr_info(vtk_csr *A, int64_t *n_global, int64_t *row_begin, int64_t *row
 /* copy this rank's CSR back (indices GLOBAL), host memory */
 int vtk_csr_download(vtk_csr *A, int32_t *indptr, int32_t *indices, void *data);
 void vtk_csr_destroy(vtk_csr *A);
+/* ---- value updates (time stepping: same sparsity pattern, new values every step) ----------
+ * SciPy statement: A.data[:] = new_values.  After a successful update A is indistinguishable
+ * from an operator freshly created with those values on the same context, tuning and layout
+ * (download, SpMV bits in every layout, line values / 4D grid tables -- rebuilt and re-checked,
+ * dropped when the new values no longer pass, regained when they pass again --, the kernels
+ * vtk_gmres picks and its result bits); everything planned from the pattern (halo plan, tiles,
+ * SELL offsets and codes, band layout) is kept.  Every allocation precedes the first overwrite:
+ * a VTK_ERR_ARG or VTK_ERR_NOMEM return leaves A as it was.  The work runs on the context's
+ * stream.  A preconditioner built before the update keeps its old factors until
+ * vtk_prec_refresh: solving with such a lagged M is legal.  A lagged block-Jacobi M applies its
+ * inverse rows whatever its mode (the tridiagonal apply of the SELL kernels takes the blocks'
+ * off-diagonals from A's rows, which are no longer the values M was factored from);
+ * vtk_bjacobi_get_mode reports INVERSE until the refresh.  (additive, ABI 6)
+ *
+ * Replace the values of A, keeping its sparsity pattern.  data: nnz_local values in the
+ * order of vtk_csr_create / vtk_csr_download, float when A was created with fp32 values,
+ * else double; host or device per ptr_kind; copied.  Rank-local, no collective. */
+int vtk_csr_update_values(vtk_csr *A, const void *data, int ptr_kind);
+/* The same for an operator made by vtk_csr_create_vlasov: regenerate this rank's values
+ * from p on the device.  dim, shape and fp32 must equal the creating parameters
+ * (VTK_ERR_ARG otherwise; VTK_ERR_STATE for an operator not created that way);
+ * vmax, E0, nu, alpha, cfl may change. */
+int vtk_csr_update_vlasov(vtk_csr *A, const vtk_vlasov_params *p);
+/* Number of successful value updates of A (0 after creation). */
+int vtk_csr_values_epoch(vtk_csr *A, int64_t *epoch);
 /* choose the SpMV layout (vtk_layout); SELL builds the copy on first use (device memory:
  * 12 B per padded entry, 8 B with f32 values) */
 int vtk_csr_set_layout(vtk_csr *A, int layout);
@@ -304,6 +329,15 @@ int vtk_linejacobi_get_compact(vtk_prec *M, int *in_use, int *available);
 /* z = M^-1 r for any preconditioner; *kind = vtk_prec_kind */
 int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int ptr_kind);
 int vtk_prec_kind_of(vtk_prec *M, int *kind);
+/* Recompute M (BJ or line Jacobi) from its operator's current values into the storage
+ * it already owns.  *epoch (nullable) = the operator epoch M now corresponds to.
+ * Block Jacobi: the setup M was created with (EXACT or MFMA), the tridiagonal check and the
+ * remembered vtk_bjacobi_set_mode request again; VTK_ERR_ARG when an explicit TRIDIAG request
+ * can no longer be met (M is refreshed and usable in INVERSE mode).  Line Jacobi: the factors
+ * and the x-invariance check again (COMPACT dropped or regained; a set_compact(0) request is
+ * kept).  VTK_ERR_SINGULAR as at creation: M is then invalid -- apply, export and vtk_gmres
+ * with it return VTK_ERR_STATE -- until a later refresh succeeds.  (additive, ABI 6) */
+int vtk_prec_refresh(vtk_prec *M, int64_t *epoch);
 /* w = M^-1 (A x): the preconditioned operator GMRES applies at every Arnoldi step (SciPy:
  * M.matvec(A @ x), iterative.py:752), computed by the launch the solver's split DCGS2 step uses
  * for this operator and preconditioner (the 4D grid-row ring kernel -- across ranks in the

@@ -181,7 +181,12 @@ BjOp bj_op(const vtk_prec *M) {
     }
     o.inv = M->d_inv;
     o.bs = M->bs;
-    if (M->tri_ok && M->mode != VTK_BJ_INVERSE) {
+    // a lagged M (not refreshed since its operator's last value update, vtk_prec_refresh) applies
+    // its inverse rows: the SELL kernels' tridiagonal apply reads only m of M's factors and takes
+    // the blocks' sub- and super-diagonals from the operator's rows -- those are A's new values
+    // now, not the ones M was factored from, and the mix is no preconditioner at all (C0 with
+    // lagged factors: no convergence).  The inverse rows are M's own data throughout.
+    if (M->tri_ok && M->mode != VTK_BJ_INVERSE && M->epoch == M->A->values_epoch) {
         o.tri = M->d_tri;
         o.tri_ld = M->tri_ld;
     }
@@ -960,6 +965,7 @@ int grid4_set(vtk_csr *A, int64_t Ny, int64_t Nvx, int64_t Nvy) {
         }
     }
     if (g.lblk < 0 && g.X < 3) return VTK_ERR_ARG;
+    A->g4_try = g;   // the geometry a value update checks its new values against (update_finish)
     DBuf tab, D, bad;
     TRY(dalloc(c, tab, grid4_tab_len(g) * sizeof(double)));
     TRY(dalloc(c, D, (size_t)n * (A->fp32 ? 4 : 8)));
@@ -1038,6 +1044,216 @@ int auto_line_band(vtk_csr *A) {
     else if (rc == VTK_ERR_NOMEM) A->ctx->err.clear();   // no memory for the tables: not detected
     else if (rc != VTK_ERR_ARG) return rc;
     return VTK_OK;
+}
+
+// ---- value updates (vtk_csr_update_values / vtk_csr_update_vlasov) -----------
+// What depends on the values: the CSR values, the SELL copy's values and the tables checked
+// against them (line-separable values, 4D grid).  Everything else of a vtk_csr is planned from
+// the pattern and stays.  update_prepare allocates all an update can need -- before the first
+// overwrite, so a VTK_ERR_NOMEM return leaves the operator as it was --, the caller then writes
+// the new values into d_data on the context's stream, and update_finish redoes the rest.
+struct UpdateScratch {
+    DBuf lsv, g4tab, g4D, bad;   // bad[0]: the line values' flags, bad[1]: the 4D grid's
+    bool want_lsv = false, want_g4 = false;
+};
+
+size_t lsv_len(const vtk_csr *A) {
+    return (size_t)A->n_local + 2 * (size_t)A->band_L + 2 * (size_t)(A->n_local / A->band_L);
+}
+
+int update_prepare(vtk_csr *A, UpdateScratch &u) {
+    vtk_ctx *c = A->ctx;
+    // the tables a fresh operator of this pattern would try: line values on a line band (f64),
+    // the 4D grid where one was tried (present or lost to earlier values)
+    u.want_lsv = A->band_L > 0 && !A->fp32;
+    u.want_g4 = A->g4_try.Ny > 0;
+    TRY(dalloc(c, u.bad, 2 * sizeof(int)));
+    if (u.want_lsv) TRY(dalloc(c, u.lsv, lsv_len(A) * sizeof(double)));
+    if (u.want_g4) {
+        TRY(dalloc(c, u.g4tab, grid4_tab_len(A->g4_try) * sizeof(double)));
+        TRY(dalloc(c, u.g4D, (size_t)A->n_local * (A->fp32 ? 4 : 8)));
+    }
+    return VTK_OK;
+}
+
+int update_finish(vtk_csr *A, UpdateScratch &u) {
+    vtk_ctx *c = A->ctx;
+    const int64_t n = A->n_local;
+    const double vb = A->fp32 ? 4.0 : 8.0;
+    const double b_csr = 4.0 * (n + 1) + (4.0 + vb) * A->nnz;   // one pass over the CSR
+    HIPCHK(c, hipMemsetAsync(u.bad.p, 0, 2 * sizeof(int), c->stream));
+    if (A->sell.d_val) {
+        Prof pf(c, "sell_refresh", -1, vb * ((double)A->nnz + (double)A->sell.entries));
+        HIPCHK(c, launch_sell_refresh(A->d_indptr, A->d_data, A->fp32, n, A->sell.d_off, A->sell.d_val, c->stream));
+    }
+    if (u.want_lsv) {
+        HIPCHK(c, hipMemsetAsync(u.lsv.p, 0, lsv_len(A) * sizeof(double), c->stream));
+        Prof pf(c, "lsv_build", -1, 2.0 * b_csr + 8.0 * (double)lsv_len(A));   // build + check passes
+        HIPCHK(c, launch_lsv_build(A->d_indptr, A->d_indices, static_cast<const double *>(A->d_data), n, (int)A->band_L,
+                                   A->band_ghost ? A->band_lblk : -1, A->band_ghost ? A->band_xord : 0,
+                                   u.lsv.as<double>(), u.bad.as<int>(), c->stream));
+    }
+    if (u.want_g4) {
+        HIPCHK(c, hipMemsetAsync(u.g4tab.p, 0, grid4_tab_len(A->g4_try) * sizeof(double), c->stream));
+        Prof pf(c, "grid4_build", -1, 2.0 * b_csr + vb * (double)n);
+        HIPCHK(c, launch_grid4_build(A->d_indptr, A->d_indices, A->d_data, A->fp32, n, A->g4_try, u.g4tab.as<double>(),
+                                     u.g4D.p, u.bad.as<int>() + 1, c->stream));
+    }
+    int hb[2] = {1, 1};
+    HIPCHK(c, hipMemcpyAsync(hb, u.bad.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->prof_on) prof_flush(c);
+    // commit, as band_check_all and grid4_set do: tables that passed replace the old ones, tables
+    // the new values fail are dropped (the structural band_L stays)
+    if (A->band_L > 0) {
+        (void)hipFree(A->d_lsv);
+        A->d_lsv = nullptr;
+        A->lsv_canon = false;
+        if (u.want_lsv && (hb[0] & 1) == 0) {
+            A->d_lsv = u.lsv.as<double>();
+            u.lsv.p = nullptr;   // owned by the operator now
+            A->lsv_canon = (hb[0] & 2) == 0;
+        }
+    }
+    if (u.want_g4) {
+        (void)hipFree(A->d_g4tab);
+        (void)hipFree(A->d_g4D);
+        A->d_g4tab = nullptr;
+        A->d_g4D = nullptr;
+        A->g4 = Grid4{};
+        if (hb[1] == 0) {
+            A->d_g4tab = u.g4tab.as<double>();
+            A->d_g4D = u.g4D.p;
+            u.g4tab.p = u.g4D.p = nullptr;
+            A->g4 = A->g4_try;
+            A->g4.tab = A->d_g4tab;
+            A->g4.D = A->d_g4D;
+        }
+    }
+    A->values_epoch += 1;
+    return VTK_OK;
+}
+
+// ---- preconditioner factors from the operator's current values ------------------------------
+// What vtk_bjacobi_create_ex computes and vtk_prec_refresh repeats, into the storage M owns
+// (d_inv; d_tri allocated here when the block size has tridiagonal factors and M has none).
+// Every allocation precedes the first overwrite.  VTK_ERR_SINGULAR: a singular block.
+int bj_factor(vtk_prec *M) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    const int bs = M->bs;
+    DBuf sing, work, flags;
+    TRY(dalloc(c, sing, sizeof(int)));
+    const bool pow2 = (bs & (bs - 1)) == 0 && bs <= 32;
+    if (!pow2) TRY(dalloc(c, work, std::max<int64_t>(M->nb, 1) * bs * bs * sizeof(double)));
+    const bool tri = bs == 2 || bs == 4 || bs == 8;
+    if (tri) {
+        TRY(dalloc(c, flags, sizeof(int)));
+        if (!M->d_tri) {
+            M->tri_ld = std::max<int64_t>(M->nb, 1) * bs;
+            HIPCHK(c, hipMalloc(&M->d_tri, 3 * M->tri_ld * sizeof(double)));
+        }
+    }
+    const int init = INT32_MAX;
+    HIPCHK(c, hipMemcpyAsync(sing.p, &init, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    {
+        Prof pf(c, M->setup == VTK_BJ_SETUP_MFMA ? "bj_setup_mfma" : "bj_setup", -1,
+                (double)M->nb * bs * bs * 8.0 + matrix_bytes(A));
+        if (M->setup == VTK_BJ_SETUP_MFMA)
+            HIPCHK(c, launch_bj_setup_mfma(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
+                                           sing.as<int>(), c->stream));
+        else
+            HIPCHK(c, launch_bj_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
+                                      sing.as<int>(), work.as<double>(), c->stream));
+    }
+    prof_flush(c);
+    int sb = 0;
+    HIPCHK(c, hipMemcpyAsync(&sb, sing.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (sb != INT32_MAX) return fail(c, VTK_ERR_SINGULAR, "vtk_bjacobi_create: singular diagonal block " + std::to_string(sb + A->row_begin / bs));
+    M->tri_ok = false;
+    if (tri) {
+        // tridiagonal blocks (the v-direction coupling of the Vlasov operators): LU factors
+        HIPCHK(c, hipMemsetAsync(flags.p, 0, sizeof(int), c->stream));
+        {
+            Prof pf(c, "bj_tri_setup", -1, (double)M->nb * bs * bs * 8.0 + 24.0 * (double)M->tri_ld + matrix_bytes(A));
+            HIPCHK(c, launch_bj_tri_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
+                                          M->d_tri, M->tri_ld, flags.as<int>(), c->stream));
+        }
+        if (c->prof_on) prof_flush(c);
+        int fl = 0;
+        HIPCHK(c, hipMemcpyAsync(&fl, flags.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        M->tri_ok = fl == 0;
+        if (!M->tri_ok) {
+            (void)hipFree(M->d_tri);
+            M->d_tri = nullptr;
+        }
+    }
+    return VTK_OK;
+}
+
+// The same for line Jacobi (vtk_linejacobi_create / vtk_prec_refresh): Thomas factors into
+// M->line.f, then the x-invariance check of the couplings; the compact tables are built in a
+// scope-owned buffer and committed (or dropped) at the end.  A vtk_linejacobi_set_compact(0)
+// request is kept.  VTK_ERR_SINGULAR: a zero or non-finite pivot.
+int line_factor(vtk_prec *M) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    DBuf bad, ext, acb;
+    const int64_t jn = M->line.jn;
+    TRY(dalloc(c, bad, sizeof(unsigned long long)));
+    TRY(dalloc(c, ext, 4 * std::max<int64_t>(jn, 1) * sizeof(unsigned long long)));
+    TRY(dalloc(c, acb, 2 * (size_t)std::max<int64_t>(jn, 1) * sizeof(double)));
+    const unsigned long long none = ~0ull;
+    std::vector<unsigned long long> hx(4 * (size_t)jn);
+    for (int64_t j = 0; j < jn; ++j) {   // min | max | min | max
+        hx[j] = none; hx[jn + j] = 0; hx[2 * jn + j] = none; hx[3 * jn + j] = 0;
+    }
+    HIPCHK(c, hipMemcpyAsync(bad.p, &none, sizeof(none), hipMemcpyHostToDevice, c->stream));
+    if (jn) HIPCHK(c, hipMemcpyAsync(ext.p, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, c->stream));
+    {
+        Prof pf(c, "line_setup", -1, 24.0 * (double)A->n_local + matrix_bytes(A));
+        HIPCHK(c, launch_line_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, M->line,
+                                    bad.as<unsigned long long>(), ext.as<unsigned long long>(), c->stream));
+    }
+    if (c->prof_on) prof_flush(c);
+    unsigned long long br = none;
+    HIPCHK(c, hipMemcpyAsync(&br, bad.p, sizeof(br), hipMemcpyDeviceToHost, c->stream));
+    if (jn) HIPCHK(c, hipMemcpyAsync(hx.data(), ext.p, hx.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (br != none) return fail(c, VTK_ERR_SINGULAR, "vtk_linejacobi_create: zero or non-finite line pivot at row " + std::to_string(br));
+    // x-invariant couplings (every line's a's bit-equal, likewise its c's): the apply forms l and
+    // g from a_j, c_j and m (16 B/row read instead of 32); lines without any a (c) take 0
+    bool inv = jn > 0;
+    std::vector<double> ac(2 * (size_t)std::max<int64_t>(jn, 1), 0.0);
+    for (int64_t j = 0; j < jn && inv; ++j) {
+        for (int w = 0; w < 2; ++w) {
+            const unsigned long long lo = hx[2 * w * jn + j], hi = hx[(2 * w + 1) * jn + j];
+            if (lo > hi) continue;   // no row of this line has the coupling
+            if (lo != hi) { inv = false; break; }
+            std::memcpy(&ac[w * jn + j], &lo, 8);
+        }
+    }
+    if (inv) HIPCHK(c, hipMemcpy(acb.p, ac.data(), ac.size() * sizeof(double), hipMemcpyHostToDevice));
+    (void)hipFree(M->line.ac);
+    M->line.ac = nullptr;
+    M->line.compact = 0;
+    if (inv) {
+        M->line.ac = acb.as<double>();
+        acb.p = nullptr;   // owned by the preconditioner now
+        M->line.compact = M->compact_req == 0 ? 0 : 1;
+    }
+    M->line_compact_ok = inv;
+    return VTK_OK;
+}
+
+// a preconditioner whose last vtk_prec_refresh met a singular block has no factors to apply or
+// export (the old ones are overwritten): VTK_ERR_STATE until a refresh succeeds
+int prec_usable(const vtk_prec *M, const char *who) {
+    if (!M || M->valid) return VTK_OK;
+    return fail(M->A->ctx, VTK_ERR_STATE, std::string(who) + ": the preconditioner's last refresh failed (singular); "
+                                                               "refresh it from non-singular values first");
 }
 
 // ---- GMRES -----------------------------------------------------------------------------------
@@ -2079,6 +2295,8 @@ int vtk_csr_create_vlasov(vtk_ctx *c, const vtk_vlasov_params *p, const int64_t 
         const int grc = grid4_set(A, p->shape[1], p->shape[2], p->shape[3]);
         if (grc != VTK_OK && grc != VTK_ERR_ARG) return grc;
     }
+    A->from_vlasov = true;   // vtk_csr_update_vlasov regenerates the values of such an operator
+    A->vparams = *p;
     *out = A;
     A = nullptr;
     return VTK_OK;
@@ -2111,6 +2329,50 @@ int vtk_csr_download(vtk_csr *A, int32_t *indptr, int32_t *indices, void *data) 
 }
 
 void vtk_csr_destroy(vtk_csr *A) { destroy_csr(A); }
+
+int vtk_csr_update_values(vtk_csr *A, const void *data, int kind) {
+    if (!A) return fail(nullptr, VTK_ERR_ARG, "vtk_csr_update_values: A is NULL");
+    vtk_ctx *c = A->ctx;
+    if ((A->nnz > 0 && !data) || (kind != VTK_PTR_HOST && kind != VTK_PTR_DEVICE))
+        return fail(c, VTK_ERR_ARG, "vtk_csr_update_values: invalid arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    UpdateScratch u;
+    TRY(update_prepare(A, u));
+    // first overwrite: the copy runs on the context's stream, behind whatever still reads the old
+    // values there (a device array must be complete, as for vtk_csr_create(VTK_PTR_DEVICE))
+    if (A->nnz)
+        HIPCHK(c, hipMemcpyAsync(A->d_data, data, (size_t)A->nnz * (A->fp32 ? sizeof(float) : sizeof(double)),
+                                 kind == VTK_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    return update_finish(A, u);
+}
+
+int vtk_csr_update_vlasov(vtk_csr *A, const vtk_vlasov_params *p) {
+    if (!A) return fail(nullptr, VTK_ERR_ARG, "vtk_csr_update_vlasov: A is NULL");
+    vtk_ctx *c = A->ctx;
+    if (!vlasov_params_ok(p)) return fail(c, VTK_ERR_ARG, "vtk_csr_update_vlasov: invalid parameters");
+    if (!A->from_vlasov) return fail(c, VTK_ERR_STATE, "vtk_csr_update_vlasov: the operator was not made by vtk_csr_create_vlasov");
+    const vtk_vlasov_params &q = A->vparams;
+    bool same = p->dim == q.dim && (p->fp32 != 0) == (q.fp32 != 0);
+    for (int k = 0; k < (p->dim == 4 ? 4 : p->dim) && same; ++k) same = p->shape[k] == q.shape[k];
+    if (!same) return fail(c, VTK_ERR_ARG, "vtk_csr_update_vlasov: dim, shape and fp32 must equal the creating parameters");
+    HIPCHK(c, hipSetDevice(c->device));
+    UpdateScratch u;
+    TRY(update_prepare(A, u));
+    {
+        const double vb = A->fp32 ? 4.0 : 8.0;
+        Prof pf(c, "vlasov_values", -1, 4.0 * (A->n_local + 1) + vb * (double)A->nnz);   // indptr read, values written
+        HIPCHK(c, launch_vlasov_values(*p, A->row_begin, A->n_local, A->d_indptr, A->d_data, c->stream));
+    }
+    TRY(update_finish(A, u));
+    A->vparams = *p;
+    return VTK_OK;
+}
+
+int vtk_csr_values_epoch(vtk_csr *A, int64_t *epoch) {
+    if (!A || !epoch) return fail(A ? A->ctx : nullptr, VTK_ERR_ARG, "vtk_csr_values_epoch: NULL argument");
+    *epoch = A->values_epoch;
+    return VTK_OK;
+}
 
 // host <-> device staging for the *_HOST forms
 struct Staged {
@@ -2167,46 +2429,11 @@ int vtk_bjacobi_create_ex(vtk_csr *A, int bs, int setup, vtk_prec **out) {
     M->device = c->device;
     M->bs = bs;
     M->nb = (A->n_local + bs - 1) / bs;
+    M->setup = setup;
     HIPCHK(c, hipMalloc(&M->d_inv, std::max<int64_t>(M->nb, 1) * bs * bs * sizeof(double)));
-    DBuf sing, work;
-    TRY(dalloc(c, sing, sizeof(int)));
+    TRY(bj_factor(M));
+    M->epoch = A->values_epoch;
     const bool pow2 = (bs & (bs - 1)) == 0 && bs <= 32;
-    if (!pow2) TRY(dalloc(c, work, std::max<int64_t>(M->nb, 1) * bs * bs * sizeof(double)));
-    const int init = INT32_MAX;
-    HIPCHK(c, hipMemcpyAsync(sing.p, &init, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    {
-        Prof pf(c, setup == VTK_BJ_SETUP_MFMA ? "bj_setup_mfma" : "bj_setup", -1,
-                (double)M->nb * bs * bs * 8.0 + matrix_bytes(A));
-        if (setup == VTK_BJ_SETUP_MFMA)
-            HIPCHK(c, launch_bj_setup_mfma(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
-                                           sing.as<int>(), c->stream));
-        else
-            HIPCHK(c, launch_bj_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
-                                      sing.as<int>(), work.as<double>(), c->stream));
-    }
-    prof_flush(c);
-    int sb = 0;
-    HIPCHK(c, hipMemcpyAsync(&sb, sing.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (sb != INT32_MAX) return fail(c, VTK_ERR_SINGULAR, "vtk_bjacobi_create: singular diagonal block " + std::to_string(sb + A->row_begin / bs));
-    if (bs == 2 || bs == 4 || bs == 8) {
-        // tridiagonal blocks (the v-direction coupling of the Vlasov operators): LU factors
-        M->tri_ld = std::max<int64_t>(M->nb, 1) * bs;
-        HIPCHK(c, hipMalloc(&M->d_tri, 3 * M->tri_ld * sizeof(double)));
-        DBuf flags;
-        TRY(dalloc(c, flags, sizeof(int)));
-        HIPCHK(c, hipMemsetAsync(flags.p, 0, sizeof(int), c->stream));
-        HIPCHK(c, launch_bj_tri_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, bs, M->d_inv,
-                                      M->d_tri, M->tri_ld, flags.as<int>(), c->stream));
-        int fl = 0;
-        HIPCHK(c, hipMemcpyAsync(&fl, flags.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        M->tri_ok = fl == 0;
-        if (!M->tri_ok) {
-            (void)hipFree(M->d_tri);
-            M->d_tri = nullptr;
-        }
-    }
     if (pow2) {
         std::vector<int32_t> rows;
         TRY(upload_tiles(c, A->h_indptr, bs, M->tiles, &rows));
@@ -2237,42 +2464,8 @@ int vtk_linejacobi_create(vtk_csr *A, int64_t stride, int64_t seg, vtk_prec **ou
     M->bs = 0;
     M->line = line_plan(A->n_local, A->row_begin, stride, seg);
     HIPCHK(c, hipMalloc(&M->line.f, 3 * std::max<int64_t>(A->n_local, 1) * sizeof(double)));
-    DBuf bad, ext;
-    const int64_t jn = M->line.jn;
-    TRY(dalloc(c, bad, sizeof(unsigned long long)));
-    TRY(dalloc(c, ext, 4 * std::max<int64_t>(jn, 1) * sizeof(unsigned long long)));
-    const unsigned long long none = ~0ull;
-    std::vector<unsigned long long> hx(4 * (size_t)jn);
-    for (int64_t j = 0; j < jn; ++j) {   // min | max | min | max
-        hx[j] = none; hx[jn + j] = 0; hx[2 * jn + j] = none; hx[3 * jn + j] = 0;
-    }
-    HIPCHK(c, hipMemcpyAsync(bad.p, &none, sizeof(none), hipMemcpyHostToDevice, c->stream));
-    if (jn) HIPCHK(c, hipMemcpyAsync(ext.p, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_line_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, M->line,
-                                bad.as<unsigned long long>(), ext.as<unsigned long long>(), c->stream));
-    unsigned long long br = none;
-    HIPCHK(c, hipMemcpyAsync(&br, bad.p, sizeof(br), hipMemcpyDeviceToHost, c->stream));
-    if (jn) HIPCHK(c, hipMemcpyAsync(hx.data(), ext.p, hx.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (br != none) return fail(c, VTK_ERR_SINGULAR, "vtk_linejacobi_create: zero or non-finite line pivot at row " + std::to_string(br));
-    // x-invariant couplings (every line's a's bit-equal, likewise its c's): the apply forms l and
-    // g from a_j, c_j and m (16 B/row read instead of 32); lines without any a (c) take 0
-    bool inv = jn > 0;
-    std::vector<double> ac(2 * (size_t)std::max<int64_t>(jn, 1), 0.0);
-    for (int64_t j = 0; j < jn && inv; ++j) {
-        for (int w = 0; w < 2; ++w) {
-            const unsigned long long lo = hx[2 * w * jn + j], hi = hx[(2 * w + 1) * jn + j];
-            if (lo > hi) continue;   // no row of this line has the coupling
-            if (lo != hi) { inv = false; break; }
-            std::memcpy(&ac[w * jn + j], &lo, 8);
-        }
-    }
-    if (inv) {
-        HIPCHK(c, hipMalloc(&M->line.ac, ac.size() * sizeof(double)));
-        HIPCHK(c, hipMemcpy(M->line.ac, ac.data(), ac.size() * sizeof(double), hipMemcpyHostToDevice));
-        M->line.compact = 1;
-    }
-    M->line_compact_ok = inv;
+    TRY(line_factor(M));
+    M->epoch = A->values_epoch;
     *out = M;
     M = nullptr;
     return VTK_OK;
@@ -2282,6 +2475,7 @@ int vtk_linejacobi_factors(vtk_prec *M, double *f, int kind) {
     if (!M || !f) return VTK_ERR_ARG;
     vtk_ctx *c = M->A->ctx;
     if (M->kind != VTK_PREC_LINE) return fail(c, VTK_ERR_STATE, "vtk_linejacobi_factors: not a line-Jacobi preconditioner");
+    TRY(prec_usable(M, "vtk_linejacobi_factors"));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (M->line.n > 0)
@@ -2295,6 +2489,7 @@ int vtk_linejacobi_set_compact(vtk_prec *M, int on) {
     if (M->kind != VTK_PREC_LINE) return fail(c, VTK_ERR_STATE, "vtk_linejacobi_set_compact: not a line-Jacobi preconditioner");
     if (on && !M->line_compact_ok) return fail(c, VTK_ERR_ARG, "vtk_linejacobi_set_compact: the x-couplings are not constant along the lines");
     M->line.compact = on ? 1 : 0;
+    M->compact_req = on ? 1 : 0;   // vtk_prec_refresh keeps a set_compact(0)
     return VTK_OK;
 }
 
@@ -2315,6 +2510,7 @@ int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int kind) { return v
 int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int kind) {
     if (!A || !x || !w || (M && M->A != A)) return fail(A ? A->ctx : nullptr, VTK_ERR_ARG, "vtk_precond_matvec: bad arguments");
     vtk_ctx *c = A->ctx;
+    TRY(prec_usable(M, "vtk_precond_matvec"));
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = A->n_local;
     Staged sx, sw;
@@ -2382,6 +2578,28 @@ int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int 
     return VTK_OK;
 }
 
+int vtk_prec_refresh(vtk_prec *M, int64_t *epoch) {
+    if (!M) return fail(nullptr, VTK_ERR_ARG, "vtk_prec_refresh: M is NULL");
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the factors are overwritten from the first launch on: M is invalid until they are whole again
+    const int64_t e = A->values_epoch;
+    const int rc = M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
+    if (rc == VTK_ERR_SINGULAR) M->valid = false;
+    if (rc != VTK_OK) return rc;
+    M->valid = true;
+    M->epoch = e;
+    if (epoch) *epoch = e;
+    if (M->kind == VTK_PREC_BJACOBI && M->mode == VTK_BJ_TRIDIAG && !M->tri_ok)
+        return fail(c, VTK_ERR_ARG, "vtk_prec_refresh: the blocks are no longer tridiagonal (or their factors failed the "
+                                    "check): the TRIDIAG request cannot be met, M applies the inverses");
+    if (M->kind == VTK_PREC_LINE && M->compact_req == 1 && !M->line_compact_ok)
+        return fail(c, VTK_ERR_ARG, "vtk_prec_refresh: the x-couplings are no longer constant along the lines: the "
+                                    "COMPACT request cannot be met, M applies the stored factors");
+    return VTK_OK;
+}
+
 int vtk_prec_kind_of(vtk_prec *M, int *kind) {
     if (!M || !kind) return VTK_ERR_ARG;
     *kind = M->kind;
@@ -2392,6 +2610,7 @@ int vtk_bjacobi_inverse(vtk_prec *M, double *inv, int kind) {
     if (!M || !inv) return VTK_ERR_ARG;
     vtk_ctx *c = M->A->ctx;
     if (M->kind != VTK_PREC_BJACOBI) return fail(c, VTK_ERR_STATE, "vtk_bjacobi_inverse: not a block-Jacobi preconditioner");
+    TRY(prec_usable(M, "vtk_bjacobi_inverse"));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(inv, M->d_inv, M->nb * M->bs * M->bs * sizeof(double), kind == VTK_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
@@ -2401,6 +2620,7 @@ int vtk_bjacobi_inverse(vtk_prec *M, double *inv, int kind) {
 int vtk_bjacobi_apply(vtk_prec *M, const double *r, double *z, int kind) {
     if (!M || !r || !z) return VTK_ERR_ARG;
     vtk_ctx *c = M->A->ctx;
+    TRY(prec_usable(M, "vtk_prec_apply"));
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = M->A->n_local;
     Staged sr, sz;
@@ -2516,6 +2736,7 @@ int vtk_csr_set_grid4(vtk_csr *A, int64_t Ny, int64_t Nvx, int64_t Nvy) {
         A->d_g4tab = nullptr;
         A->d_g4D = nullptr;
         A->g4 = Grid4{};
+        A->g4_try = Grid4{};
         return VTK_OK;
     }
     const int rc = grid4_set(A, Ny, Nvx, Nvy);
@@ -2596,6 +2817,7 @@ int vtk_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
     if (!A || !b || !x || !info) return VTK_ERR_ARG;
     vtk_ctx *c = A->ctx;
     if (M && M->A != A) return fail(c, VTK_ERR_ARG, "vtk_gmres: preconditioner built for another operator");
+    TRY(prec_usable(M, "vtk_gmres"));
     if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail(c, VTK_ERR_ARG, "vtk_gmres: tolerances must be non-negative");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = A->n_local;

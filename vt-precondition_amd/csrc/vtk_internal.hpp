@@ -290,6 +290,15 @@ struct vtk_csr {
     std::vector<int64_t> band_scnt, band_soff, band_rcnt, band_roff;
     int64_t band_off_first = -1, band_off_last = -1;    // send offsets of the first / last line
     int64_t band_off_left = -1, band_off_right = -1;    // recv offsets of the left / right ghost
+    // value updates (vtk_csr_update_values / vtk_csr_update_vlasov): the pattern and
+    // everything planned from it stay, the values and the tables checked against them are redone
+    int64_t values_epoch = 0;                           // successful updates since creation
+    bool from_vlasov = false;                           // made by vtk_csr_create_vlasov ...
+    vtk_vlasov_params vparams{};                        // ... from these parameters (the last update's)
+    // the 4D grid geometry last tried on this operator (grid4_set; pointers null): an update
+    // re-checks the new values against it, so tables lost to one set of values come back with the
+    // next that passes.  Ny 0: none (never tried, or cleared by vtk_csr_set_grid4)
+    vtk::Grid4 g4_try;
 };
 
 struct vtk_prec {
@@ -313,6 +322,12 @@ struct vtk_prec {
     int kind = VTK_PREC_BJACOBI;
     vtk::LineOp line;
     bool line_compact_ok = false;   // x-invariant couplings found at setup (line.ac valid)
+    // vtk_prec_refresh: what creation was asked for, and the operator values the
+    // factors were computed from
+    int setup = VTK_BJ_SETUP_EXACT;  // resolved vtk_bj_setup (EXACT or MFMA)
+    int compact_req = -1;            // vtk_linejacobi_set_compact's last request (-1: none)
+    int64_t epoch = 0;               // vtk_csr::values_epoch of the values M was factored from
+    bool valid = true;               // false after a refresh that met a singular block / zero pivot
 };
 
 namespace vtk {
@@ -440,6 +455,13 @@ hipError_t launch_vlasov_counts(const vtk_vlasov_params &p, int64_t r0, int64_t 
 hipError_t launch_vlasov_fill(const vtk_vlasov_params &p, int64_t r0, int64_t nrows,
                               const int32_t *indptr, int32_t *indices, void *data,
                               hipStream_t s);
+// value updates (vtk_update.hip): the SELL copy's values from the CSR values, the pattern (off,
+// columns, codes) untouched -- k_sell_fill's values bit for bit; and the Vlasov generator's values
+// of rows [r0, r0 + nrows) into data at the existing indptr, no column written
+hipError_t launch_sell_refresh(const int32_t *indptr, const void *data, int fp32, int64_t n, const int64_t *off,
+                               void *val, hipStream_t s);
+hipError_t launch_vlasov_values(const vtk_vlasov_params &p, int64_t r0, int64_t nrows, const int32_t *indptr,
+                                void *data, hipStream_t s);
 hipError_t launch_exclusive_scan(const int32_t *in, int32_t *out, int64_t n, void *tmp,
                                  size_t *tmp_bytes, hipStream_t s);
 hipError_t launch_remap_cols(int32_t *indices, int64_t nnz, int64_t row_begin, int64_t n_local,

@@ -332,6 +332,51 @@ class CsrOperator:
         check(lib().vtk_csr_download(self._h, _np_ptr(ip), _np_ptr(ix), _np_ptr(d)), self.ctx.handle)
         return ip, ix[:self.nnz], d[:self.nnz]
 
+    def update_values(self, data):
+        """SciPy's ``A.data[:] = data``: replace the values, keep the sparsity pattern
+        (``vtk_csr_update_values``).  ``data``: ``nnz`` values in the order of
+        :func:`csr_matrix` / :meth:`download` -- a NumPy array or a torch tensor on the context's
+        device, float32 for an fp32 operator, else float64 (anything else: ValueError, before any
+        device work).  Afterwards the operator equals one freshly built from these values;
+        preconditioners keep their old factors until their ``refresh()``."""
+        want = np.float32 if self.fp32 else np.float64
+        if _is_device(data):
+            import torch
+            if data.dtype != (torch.float32 if self.fp32 else torch.float64):
+                raise ValueError(f"update_values: dtype {data.dtype}, the operator stores {np.dtype(want).name}")
+            if data.dim() != 1 or data.numel() != self.nnz:
+                raise ValueError(f"update_values: {tuple(data.shape)} values given, the operator has nnz = {self.nnz}")
+            if data.device.index != self.ctx.device:
+                raise ValueError(f"update_values: tensor on {data.device}, the context is on cuda:{self.ctx.device}")
+            data = data.contiguous()
+            # the library copies on its own stream: the tensor must be complete first
+            torch.cuda.current_stream(data.device).synchronize()
+            check(lib().vtk_csr_update_values(self._h, C.c_void_p(data.data_ptr()), _abi.PTR_DEVICE),
+                  self.ctx.handle)
+            return self
+        a = np.asarray(data)
+        if a.dtype != want:
+            raise ValueError(f"update_values: dtype {a.dtype}, the operator stores {np.dtype(want).name}")
+        if a.ndim != 1 or a.shape[0] != self.nnz:
+            raise ValueError(f"update_values: {a.shape} values given, the operator has nnz = {self.nnz}")
+        a = np.ascontiguousarray(a)
+        check(lib().vtk_csr_update_values(self._h, _np_ptr(a), _abi.PTR_HOST), self.ctx.handle)
+        return self
+
+    def update_vlasov(self, params: VlasovParams):
+        """The same for an operator made by :func:`vlasov_operator`: regenerate the values from
+        ``params`` on the device (``vtk_csr_update_vlasov``).  dim, shape and fp32 must be the
+        creating ones; vmax, E0, nu, alpha and cfl may change."""
+        check(lib().vtk_csr_update_vlasov(self._h, C.byref(params)), self.ctx.handle)
+        return self
+
+    @property
+    def values_epoch(self) -> int:
+        """Number of successful value updates (0 after creation)."""
+        e = C.c_int64()
+        check(lib().vtk_csr_values_epoch(self._h, C.byref(e)), self.ctx.handle)
+        return e.value
+
     def close(self):
         if getattr(self, "_h", None):
             lib().vtk_csr_destroy(self._h)
@@ -470,6 +515,15 @@ def vlasov_operator(params: VlasovParams, *, ctx: Context | None = None, offsets
 BJ_MODES = {"auto": 0, "inverse": 1, "tridiag": 2}
 
 
+def _refresh(M):
+    e = C.c_int64(M._epoch)
+    try:
+        check(lib().vtk_prec_refresh(M._h, C.byref(e)), M.A.ctx.handle)
+    finally:
+        M._epoch = e.value   # written by the library once the factors are whole (also on ValueError)
+    return M
+
+
 class BlockJacobi:
     """Block-Jacobi preconditioner M = blockdiag(A)^-1 (SciPy: a LinearOperator whose matvec
     applies the bs x bs diagonal-block inverses).  ``vtk_bjacobi_create``.
@@ -499,7 +553,22 @@ class BlockJacobi:
         self.bs = bs
         self.shape = A.shape
         self.dtype = np.dtype(np.float64)
+        self._epoch = A.values_epoch
         self.set_mode(mode)
+
+    def refresh(self):
+        """Recompute the inverses (and tridiagonal factors) from the operator's current values into
+        the storage this preconditioner owns (``vtk_prec_refresh``): the setup it was created
+        with and the mode request again.  LinAlgError on a singular block -- the preconditioner
+        is then unusable (VtkError, status ERR_STATE) until a later refresh succeeds; ValueError
+        when an explicit "tridiag" request can no longer be met (refreshed, applies "inverse")."""
+        return _refresh(self)
+
+    @property
+    def values_epoch(self) -> int:
+        """``A.values_epoch`` of the values the factors were computed from (a lagged
+        preconditioner -- older than ``A.values_epoch`` -- is legal)."""
+        return self._epoch
 
     def set_mode(self, mode: str):
         check(lib().vtk_bjacobi_set_mode(self._h, BJ_MODES[mode]), self.A.ctx.handle)
@@ -579,6 +648,19 @@ class LineJacobi:
         self.seg = int(seg)
         self.shape = A.shape
         self.dtype = np.dtype(np.float64)
+        self._epoch = A.values_epoch
+
+    def refresh(self):
+        """Recompute the Thomas factors from the operator's current values into the storage this
+        preconditioner owns and re-run the x-invariance check (``vtk_prec_refresh``): the compact
+        apply is dropped or regained accordingly, a ``set_compact(False)`` is kept.  LinAlgError
+        on a zero pivot -- unusable (VtkError, status ERR_STATE) until a later refresh succeeds."""
+        return _refresh(self)
+
+    @property
+    def values_epoch(self) -> int:
+        """``A.values_epoch`` of the values the factors were computed from."""
+        return self._epoch
 
     @property
     def handle(self):

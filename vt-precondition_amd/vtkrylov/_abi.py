@@ -83,6 +83,10 @@ PROTOTYPES = {
     "vtk_csr_info": (C.c_int, [P, I64P, I64P, I64P, I64P, I64P]),
     "vtk_csr_download": (C.c_int, [P, P, P, P]),
     "vtk_csr_destroy": (None, [P]),
+    "vtk_csr_update_values": (C.c_int, [P, P, C.c_int]),
+    "vtk_csr_update_vlasov": (C.c_int, [P, C.POINTER(VlasovParams)]),
+    "vtk_csr_values_epoch": (C.c_int, [P, I64P]),
+    "vtk_prec_refresh": (C.c_int, [P, I64P]),
     "vtk_spmv": (C.c_int, [P, P, P, C.c_int]),
     "vtk_bjacobi_create": (C.c_int, [P, C.c_int, C.POINTER(P)]),
     "vtk_bjacobi_inverse": (C.c_int, [P, P, C.c_int]),
