@@ -342,7 +342,11 @@ int vtk_prec_refresh(vtk_prec *M, int64_t *epoch);
  * M.matvec(A @ x), iterative.py:752), computed by the launch the solver's split DCGS2 step uses
  * for this operator and preconditioner (the 4D grid-row ring kernel -- across ranks in the
  * solver's interior / boundary form --, else the SpMV with the BJ epilogue, else SpMV then
- * apply); M may be NULL (w = A x).  Bit-identical across those forms: the kernel-level pin. */
+ * apply); M may be NULL (w = A x).  Bit-identical across those forms, and to vtk_bjacobi_apply
+ * of vtk_spmv, with the INVERSE apply: the kernel-level pin.  With the TRIDIAG apply the SELL
+ * kernels (and the ring kernel) read m alone and form l_i = sub_i m_{i-1} from the row's own
+ * entry where the stored factor is sub_i / u_{i-1}: bit-identical among themselves, equal to the
+ * CSR-layout epilogue and to vtk_bjacobi_apply (both solve with the stored l | m | g) to rounding. */
 int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int ptr_kind);
 
 /* ---- solver --------------------------------------------------------------------------- */
