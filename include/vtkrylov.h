@@ -177,7 +177,8 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * fail_step.
  * VTK_ERR_ARG for an unknown key; a VTK_<KEY> variable of a key removed in round 5 draws a
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
- * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows) */
+ * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
+ * band_opt bit 5, odd band steps walking their line ranges the other way round, at every size) */
 int vtk_ctx_set_tuning(vtk_ctx *ctx, const char *key, int value);
 int vtk_ctx_get_tuning(vtk_ctx *ctx, const char *key, int *value);
 /* rank 0 creates the 128-byte RCCL unique id; the caller broadcasts it (any transport) */

@@ -1462,6 +1462,10 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
     // basis vectors: on smaller ones (C2, the C3 slabs) more of the basis stays in the Infinity
     // Cache between steps, so the DMA's issue and L2 over-fetch cost more than the latency it hides
     // and the halo lines' second read hits anyway (band_long_rows, vtk_internal.hpp)
+    // bit 5 (odd steps walk the other way round) stays at every size: in-process A/B 63 vs 31,
+    // median ms per solve (spread of the eight bit-5-off solves): C3 36.62 vs 37.37 (0.18), C3/2
+    // slab 18.86 vs 18.95 (0.02), C2 10.21 vs 10.28 (0.08), C3/8 slab 6.16 vs 6.23 (0.04)
+    // (profiles/serpentine_ab*.json)
     const int band_opt = band_lsv && s.A->lsv_canon && band_canon
                              ? (n >= c->tune.band_long_rows ? c->tune.band_opt : c->tune.band_opt & ~(8 | 16))
                              : 0;

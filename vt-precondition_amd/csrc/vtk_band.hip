@@ -149,7 +149,14 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
     // the other's x-halo line) at the same time, at the start or at the end of both walks: the
     // second read finds the line in the Infinity Cache instead of HBM.  (The dots then sum an
     // odd range's lines in reverse order: not the bits of the forward walk, within the DCGS2 bars.)
-    const bool rev = (a.opt & 16) && (rb & 1);
+    // opt bit 5 (SERP): odd steps walk the other way round, on top of bit 4's range parity, so step
+    // j + 1 begins with the lines step j touched last -- the rows it reads there (V_k, v_j, both w,
+    // D, m) were read or written a few hundred MB of traffic earlier and are still in the Infinity
+    // Cache.  J is a template parameter: no run-time cost.  Bit 4's pairing holds:
+    // both workgroups at a range boundary flip together.  The non-temporal loads and write-through
+    // stores leave their lines there as plain ones do (profiles/serpentine_probe.txt), so the load
+    // and store policies are the same at both ends of a walk as in its middle
+    const bool rev = ((a.opt & 16) && (rb & 1)) != ((a.opt & 32) && (J & 1));
     // kind 1 / 2: the left / right x-halo line (a forward walk's first / last iteration)
     auto line_of = [&](int it, int &kind) {
         if (rev) {

@@ -177,18 +177,25 @@ struct Tuning {
     int band_lsv = 1;         // solver launches read the line-separable values (else SELL values)
     int sell_canon = 1;       // ... and canonical rows' columns from the line index (no codes)
     int band_canon = 1;       // the band step reads no codes on canonical rows
-    int band_opt = 31;        // band step variant bits (vtk_band.hip k_band_step OPT; in-process A/B
+    int band_opt = 63;        // band step variant bits (vtk_band.hip k_band_step OPT; in-process A/B
                               // C3: SpMV operands prefetched j00 254 -> 217 us, + three workgroups per
                               // CU for j <= BAND_J3: j00 190, j01 283 -> 246 us; solve 42.66 -> 42.31 ms;
                               // round 6: bit 2, a line range's two parts on one XCD: 40.56 -> 40.30 ms;
                               // bit 3, LDS-DMA L2 prefetch for J > BAND_PF: j13-j18 -21..-50 us each;
                               // bit 4, odd line ranges walk backwards: 39.98 -> 39.81 ms, C3/8 slab
-                              // 6.652 vs 6.676 ms (neutral).  Since round 6 also across ranks)
+                              // 6.652 vs 6.676 ms (neutral).  Since round 6 also across ranks;
+                              // bit 5 (32), odd steps walk the other way round -- a step starts on the
+                              // lines the previous one touched last, still in the Infinity Cache
+                              // (DESIGN.md §3i): C3 37.37 -> 36.62 ms (two runs: -2.0 %, -1.7 %), at
+                              // every size: C2 10.28 -> 10.21, C3/2 slab 18.95 -> 18.86, C3/8 slab
+                              // 6.23 -> 6.16 ms (profiles/serpentine_ab*.json); every step reversed
+                              // instead of every other one: 38.79 vs 38.78 ms, nothing)
     int band_long_rows = 16000000;   // band_opt bits 3 and 4 only on basis vectors of >= this many rows
                               // (in-process A/B, round 6: bit 3 on vs off, C3 20M rows 39.30 vs 39.78 ms,
                               // C3/2 slab 10M 20.20 vs 20.09, C2 5M 10.98 vs 10.86, C3/8 slab 2.5M 6.53
                               // vs 6.51; bit 4 on vs off, C3 39.24 vs 39.34, C3/2 20.13 vs 20.00, C3/4
-                              // 11.02 vs 10.95, C2 10.92 vs 10.87)
+                              // 11.02 vs 10.95, C2 10.92 vs 10.87).  Bit 5 does not follow it: faster
+                              // at every size measured
     int lsv_ring = 2048;      // > 0: the line path's table SpMV with x staged through LDS, ~that many
                               // workgroups (in-process A/B, C3 line solve: 8.64 -> 8.26 ms; 167 -> 105 us)
     int prof_perj = 0;        // profile class per band step index (band_step_jNN)
