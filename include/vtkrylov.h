@@ -174,11 +174,13 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * nowhere else (fail_step is a test hook: this rank fails its DCGS2 step of that index in the
  * first cycle, vtk_gmres).  Keys: band, band_lsv, sell_canon, band_canon, band_opt, band_long_rows, lsv_ring,
  * prof_perj, comm_solo, auto_band, grid4, c4_fused, g4_ring, g4_gr, g4_fast, line_fuse, cyc_ring,
- * fail_step.
+ * bcg_fuse, fail_step.
  * VTK_ERR_ARG for an unknown key; a VTK_<KEY> variable of a key removed in round 5 draws a
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
  * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
- * band_opt bit 5, odd band steps walking their line ranges the other way round, at every size) */
+ * band_opt bit 5, odd band steps walking their line ranges the other way round, at every size;
+ * bcg_fuse: vtk_bicgstab forms phat = M p and shat = M s inside its vector kernels for block Jacobi
+ * with bs in {1, 2, 4, 8} -- 0: the separate apply, the same bits) */
 int vtk_ctx_set_tuning(vtk_ctx *ctx, const char *key, int value);
 int vtk_ctx_get_tuning(vtk_ctx *ctx, const char *key, int *value);
 /* rank 0 creates the 128-byte RCCL unique id; the caller broadcasts it (any transport) */
@@ -368,6 +370,28 @@ int vtk_gmres_set_orth(vtk_ctx *ctx, int orth);
 /* on (default) / off: the line-band DCGS2 step when the operator and preconditioner allow it
  * (vtk_csr_set_line_band); off keeps the separate update pass and fused SpMV step */
 int vtk_gmres_set_band(vtk_ctx *ctx, int on);
+
+/* scipy.sparse.linalg.bicgstab semantics (iterative.py, bicgstab, callback=None): right-
+ * preconditioned BiCGStab, M approximating A^-1 (NULL: none); x holds x0 on entry.  info as
+ * SciPy's: 0 converged (||r|| or ||s|| of the recurrence below max(atol, rtol ||b||)), -10 the
+ * rho breakdown, -11 the omega or <rtilde, v> breakdown, else maxiter (<= 0: 10 n; at most
+ * 2^29 - 3 iterations are run).  x changes only by the iteration's two updates: on a breakdown it
+ * holds the last completed iterate.  Fixed memory: seven work vectors of n_local doubles,
+ * allocated for the call.  Every test and every scalar of the loop stays on the device; the
+ * host issues iterations ahead and watches a mapped stop flag, with no synchronisation per
+ * iteration.  ONE RANK ONLY: on a context whose communicator has more than one rank the call
+ * returns VTK_ERR_STATE (the failure-vote protocol of vtk_gmres would need its own design
+ * here).  (additive, ABI 6) */
+typedef struct {
+    int64_t iterations;    /* v = A M p products computed                          */
+    double rnorm;          /* true residual ||b - A x|| of the returned x          */
+    double bnorm, atol_eff;
+    double t_solve;        /* seconds, as vtk_stats.t_solve                        */
+    double bytes_moved;    /* algorithmic bytes, DESIGN.md §4 conventions          */
+    int half_step;         /* 1: left through the ||s|| test                       */
+} vtk_bicgstab_stats;
+int vtk_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, double atol,
+                 int64_t maxiter, int ptr_kind, int *info, vtk_bicgstab_stats *stats);
 
 /* ---- kernel profile (measurement) ------------------------------------------
  * When enabled, every kernel the library launches is bracketed by HIP events on the

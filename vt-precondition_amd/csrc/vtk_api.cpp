@@ -1,5 +1,6 @@
 // vtk_api.cpp — C-ABI of libvtkrylov.so: contexts, RCCL communicator, CSR operator, block-Jacobi
-// preconditioner and the restarted GMRES driver (host orchestration of the gfx950 kernels).
+// preconditioner, the restarted GMRES driver and the BiCGStab driver (run_bicgstab, at the end of
+// the solver section) -- host orchestration of the gfx950 kernels.
 //
 // The driver restates scipy.sparse.linalg.gmres (scipy/sparse/linalg/_isolve/iterative.py:
 // 692-841) with every vector operation and every reduction on the device; the host only keeps
@@ -85,6 +86,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {"prof_perj", &Tuning::prof_perj}, {"comm_solo", &Tuning::comm_solo}, {"auto_band", &Tuning::auto_band},
     {"grid4", &Tuning::grid4}, {"c4_fused", &Tuning::c4_fused}, {"g4_ring", &Tuning::g4_ring},
     {"g4_gr", &Tuning::g4_gr}, {"g4_fast", &Tuning::g4_fast}, {"line_fuse", &Tuning::line_fuse}, {"cyc_ring", &Tuning::cyc_ring},
+    {"bcg_fuse", &Tuning::bcg_fuse},
     {"fail_step", &Tuning::fail_step},
 };
 // switches of earlier rounds whose alternative lost its A/B: an environment that
@@ -2045,6 +2047,175 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
     return done(rnorm <= atol ? 0 : (int)std::min<int64_t>(maxiter, INT32_MAX));   // :840
 }
 
+// ---- BiCGStab ----------------------------------------------------------------------------------
+// scipy.sparse.linalg.bicgstab (iterative.py) with every vector operation, every reduction and
+// every test of the loop on the device (vtk_bicgstab.hip).  The host enqueues whole
+// iterations, LOOKAHEAD of them ahead of the device, and watches the mapped stop flag; kernels
+// tagged after the stop return at entry.  One rank.
+static_assert(sizeof(BicgState) <= sizeof(GmresState), "the pinned state mirror holds either solver's record");
+
+// bytes per row of M as the standalone apply and the fused k_bcg_p / k_bcg_s read it: the stored
+// l | m | g of tridiagonal blocks (bj_row_bytes counts the SELL epilogue's m alone), the inverse
+// rows, the line factors
+double bcg_prec_row_bytes(const vtk_prec *M) {
+    if (M && M->kind == VTK_PREC_BJACOBI && bj_op(M).tri) return 24.0;
+    return bj_row_bytes(M);
+}
+
+int run_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, double atol, int64_t maxiter,
+                 int *info, vtk_bicgstab_stats *stout) {
+    vtk_ctx *c = A->ctx;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t n = A->n_local, N = A->n_global;
+    if (N < 1) return fail(c, VTK_ERR_ARG, "vtk_bicgstab: empty system");
+    if (maxiter <= 0) maxiter = N * 10;                     // iterative.py: maxiter None -> n * 10
+    const int info_max = (int)std::min<int64_t>(maxiter, INT32_MAX);
+    maxiter = std::min(maxiter, BCG_MAX_ITERS);
+    const int64_t ld = round_up(std::max<int64_t>(n, 1), 64);
+    const int G = grid_for(c, vector_grid(n));
+    // work: r (s in place) | rtilde | p | v | t | phat | shat, then the device state
+    DBuf work;
+    TRY(dalloc(c, work, (7 * (size_t)ld + 16) * sizeof(double)));
+    double *r = work.as<double>(), *rtilde = r + ld, *p = rtilde + ld, *v = p + ld, *t = v + ld;
+    double *phat = M ? t + ld : p, *shat = M ? t + 2 * ld : r;   // no preconditioner: M p = p, M s = s
+    BicgState *ds = reinterpret_cast<BicgState *>(r + 7 * (size_t)ld);
+    BicgState *hs = reinterpret_cast<BicgState *>(c->h_state);
+    const int *stop = &ds->stop;
+    volatile int *mirror = c->h_stop;
+    // partial-sum slots (vtk_ctx::d_part, GMAX each)
+    double *p_vv = c->d_part, *p_rv = c->d_part + GMAX, *p_ss = c->d_part + 2 * GMAX, *p_tt = c->d_part + 3 * GMAX;
+    double *p_ts = c->d_part + 4 * GMAX, *p_rr = c->d_part + 5 * GMAX, *p_rho = c->d_part + 6 * GMAX;
+    double *p_b = c->d_part + 7 * GMAX;
+    const Red none{nullptr, 0};
+    const double n8 = 8.0 * n;
+    const double b_csr = solver_matrix_bytes(A);
+    const double b_inv = bcg_prec_row_bytes(M) * n;
+    const BjOp bj = bj_op(M);
+    const bool fuse = M && c->tune.bcg_fuse && bcg_fusable(bj);
+
+    // ||b|| and `x.any()`: the one host decision before the loop (bnrm2 == 0, r = b or b - A x)
+    { Prof pf(c, "dot", -1, n8);
+      HIPCHK(c, launch_dot(b, nullptr, n, p_b, G, c->stream)); }
+    HIPCHK(c, launch_finalize(Red{p_b, G}, &c->d_scal[0], 1, c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_scal[2], 0, sizeof(double), c->stream));
+    { Prof pf(c, "any", -1, n8);
+      HIPCHK(c, launch_any_nonzero(x, n, &c->d_scal[2], c->stream)); }
+    double h3[3] = {0.0, 0.0, 0.0};
+    HIPCHK(c, hipMemcpyAsync(h3, c->d_scal, sizeof(h3), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double bnrm2 = h3[0];
+    const bool r_is_b = h3[2] == 0.0;
+    atol = std::max(atol, rtol * bnrm2);                    // _get_atol_rtol
+    vtk_bicgstab_stats st{};
+    st.bnorm = bnrm2;
+    st.atol_eff = atol;
+    auto done = [&](int inf) {
+        *info = inf;
+        st.t_solve = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (stout) *stout = st;
+        return VTK_OK;
+    };
+    if (bnrm2 == 0.0) {                                     // return postprocess(b), 0
+        HIPCHK(c, hipMemcpyAsync(x, b, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        prof_flush(c);
+        return done(0);
+    }
+    // r = b - A x if x.any() else b; rtilde = r
+    Red rr0{p_b, G};
+    if (r_is_b) {
+        HIPCHK(c, hipMemcpyAsync(r, b, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        TRY(halo_exchange(A, x));
+        Prof pf(c, "spmv_resid", -1, b_csr + 3 * n8);
+        const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, x), A);
+        HIPCHK(c, launch_spmv(in, EPI_RESID, r, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream));
+        rr0 = Red{p_rr, spmv_grid(in)};
+    }
+    HIPCHK(c, hipMemcpyAsync(rtilde, r, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    std::memset(hs, 0, sizeof(BicgState));
+    hs->stop = BCG_RUN;
+    HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(BicgState), hipMemcpyHostToDevice, c->stream));
+    *mirror = BCG_RUN;
+    { Prof pf(c, "bcg_scalar", 0, 8.0 * rr0.cnt);
+      HIPCHK(c, launch_bcg_scalar(BCG_PH_INIT, 0, 0, info_max, atol, rr0, none, none, none, ds, c->d_stop, stop, 0, c->stream)); }
+
+    hipEvent_t ev[LOOKAHEAD + 1];
+    for (auto &e : ev) e = nullptr;
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i <= LOOKAHEAD; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } eg{ev};
+    for (auto &e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+
+    // products of the loop: y = A x, part0 = sum y^2, part1 = sum v0 y
+    auto product = [&](const double *xin, double *y, const double *v0, double *part0, double *part1, int tag, int &cnt) -> int {
+        TRY(halo_exchange(A, xin));
+        Prof pf(c, "spmv_w", tag, b_csr + 3 * n8);
+        const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, xin), A);
+        HIPCHK(c, launch_spmv(in, EPI_PREC, y, nullptr, BjOp{}, v0, part0, part1, stop, tag, c->stream));
+        cnt = spmv_grid(in);
+        return VTK_OK;
+    };
+    auto apply = [&](const double *in, double *out, int tag) -> int {
+        Prof pf(c, prec_cls(M), tag, b_inv + 2 * n8);
+        HIPCHK(c, launch_bj_apply(bj, n, in, out, nullptr, nullptr, nullptr, G, stop, tag, c->stream));
+        return VTK_OK;
+    };
+    for (int64_t k = 0; k < maxiter; ++k) {
+        const int t1 = bcg_tag(k, 1), t3 = bcg_tag(k, 3);
+        const int first = k == 0 ? 1 : 0;
+        int cnt = 0;
+        // p = r + beta (p - omega v); phat = M p; v = A phat; rv = <rtilde, v>; alpha
+        { Prof pf(c, "bcg_p", t1, (first ? 2 : 4) * n8 + (fuse ? b_inv + n8 : 0.0));
+          HIPCHK(c, launch_bcg_p(ds, first, n, r, v, p, fuse ? &bj : nullptr, phat, G, stop, t1, c->stream)); }
+        if (M && !fuse) TRY(apply(p, phat, t1));
+        TRY(product(phat, v, rtilde, p_vv, p_rv, t1, cnt));
+        { Prof pf(c, "bcg_scalar", t1, 8.0 * cnt);
+          HIPCHK(c, launch_bcg_scalar(BCG_PH_A, k, 0, info_max, atol, none, Red{p_rv, cnt}, none, none, ds, c->d_stop, stop, t1, c->stream)); }
+        // s = r - alpha v (in r); ||s|| < atol: the half-step exit
+        { Prof pf(c, "bcg_s", t1, 3 * n8 + (fuse ? b_inv + n8 : 0.0));
+          HIPCHK(c, launch_bcg_s(ds, n, r, v, fuse ? &bj : nullptr, shat, p_ss, G, stop, t1, c->stream)); }
+        { Prof pf(c, "bcg_scalar", t1, 8.0 * G);
+          HIPCHK(c, launch_bcg_scalar(BCG_PH_B, k, 0, info_max, atol, Red{p_ss, G}, none, none, none, ds, c->d_stop, stop, t1, c->stream)); }
+        // shat = M s; t = A shat; omega = <t, s> / <t, t>; x += alpha phat + omega shat; r = s - omega t
+        if (M && !fuse) TRY(apply(r, shat, t3));
+        TRY(product(shat, t, r, p_tt, p_ts, t3, cnt));
+        { Prof pf(c, "bcg_x", t3, 8 * n8 + 16.0 * cnt);
+          HIPCHK(c, launch_bcg_x(ds, Red{p_ts, cnt}, Red{p_tt, cnt}, n, x, phat, shat, r, t, rtilde, p_rr, p_rho, G, stop, t3, c->stream)); }
+        { Prof pf(c, "bcg_scalar", t3, 16.0 * cnt + 16.0 * G);
+          HIPCHK(c, launch_bcg_scalar(BCG_PH_C, k, k + 1 == maxiter ? 1 : 0, info_max, atol, Red{p_ts, cnt}, Red{p_tt, cnt},
+                                      Red{p_rr, G}, Red{p_rho, G}, ds, c->d_stop, stop, t3, c->stream)); }
+        HIPCHK(c, hipEventRecord(ev[k % (LOOKAHEAD + 1)], c->stream));
+        if (k >= LOOKAHEAD) {
+            HIPCHK(c, hipEventSynchronize(ev[(k - LOOKAHEAD) % (LOOKAHEAD + 1)]));
+            if (*mirror != BCG_RUN) break;
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(hs, ds, sizeof(BicgState), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (hs->stop == BCG_RUN) return fail(c, VTK_ERR_HIP, "vtk_bicgstab: the loop ended without a stop record");
+    const int64_t its = hs->iterations;
+    if (hs->half_step) {   // x += alpha phat: the flag sits at that iteration's half-step tag
+        Prof pf(c, "bcg_x", -1, 3 * n8);
+        HIPCHK(c, launch_bcg_half_x(ds, n, x, phat, G, stop, bcg_tag(its - 1, 2), c->stream));
+    }
+    // the true residual of the returned x (t is free now)
+    {
+        TRY(halo_exchange(A, x));
+        const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, x), A);
+        { Prof pf(c, "spmv_resid", -1, b_csr + 3 * n8);
+          HIPCHK(c, launch_spmv(in, EPI_RESID, t, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream)); }
+        HIPCHK(c, launch_finalize(Red{p_rr, spmv_grid(in)}, &c->d_scal[1], 1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&st.rnorm, &c->d_scal[1], sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (c->prof_on) prof_flush(c, hs->stop);
+    st.iterations = its;
+    st.half_step = hs->half_step;
+    // algorithmic bytes: per iteration two products, two applies, p (4 vectors), s (3), x (8)
+    const double per_it = 2 * (b_csr + 3 * n8) + (M ? 2 * (b_inv + 2 * n8) : 0.0) + 15 * n8;
+    st.bytes_moved = per_it * (double)its + 2 * (b_csr + 3 * n8) + 4 * n8;
+    return done(hs->info);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2829,6 +3000,29 @@ int vtk_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
     TRY(stage_in(c, b, n, kind, sb));
     TRY(stage_in(c, x, n, kind, sx));
     TRY(run_gmres(A, M, sb.d, sx.d, rtol, atol, restart, maxiter, info, st));
+    if (kind == VTK_PTR_HOST) {
+        HIPCHK(c, hipMemcpyAsync(x, sx.d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VTK_OK;
+}
+
+int vtk_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, double atol, int64_t maxiter,
+                 int kind, int *info, vtk_bicgstab_stats *st) {
+    if (!A || !b || !x || !info) return VTK_ERR_ARG;
+    vtk_ctx *c = A->ctx;
+    if (M && M->A != A) return fail(c, VTK_ERR_ARG, "vtk_bicgstab: preconditioner built for another operator");
+    TRY(prec_usable(M, "vtk_bicgstab"));
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail(c, VTK_ERR_ARG, "vtk_bicgstab: tolerances must be non-negative");
+    if (c->world > 1)
+        return fail(c, VTK_ERR_STATE, "vtk_bicgstab: one rank only (this context's communicator has " +
+                                          std::to_string(c->world) + " ranks); use vtk_gmres across ranks");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = A->n_local;
+    Staged sb, sx;
+    TRY(stage_in(c, b, n, kind, sb));
+    TRY(stage_in(c, x, n, kind, sx));
+    TRY(run_bicgstab(A, M, sb.d, sx.d, rtol, atol, maxiter, info, st));
     if (kind == VTK_PTR_HOST) {
         HIPCHK(c, hipMemcpyAsync(x, sx.d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }

@@ -35,6 +35,24 @@ struct GmresState {
     int pad_;
 };
 
+// BiCGStab (vtk_bicgstab; vtk_bicgstab.hip): the scalars of SciPy's loop, kept on
+// the device by k_bcg_scalar.  stop is the flag the solve's kernels test: a kernel tagged above it
+// returns at entry.  Tags of iteration k: 4k + 1 up to the ||s|| test, 4k + 2 the half-step
+// exit's x update (runs only when stop == its tag), 4k + 3 the rest.
+struct BicgState {
+    double rho, rho_prev, alpha, omega, beta, rv;
+    double rnorm, snorm;          // ||r|| and ||s|| of the recurrence (the exit tests)
+    long long iterations;         // v = A M p products that count (vtk_bicgstab_stats::iterations)
+    int info;                     // SciPy's return code once stopped
+    int half_step;                // left through the ||s|| test
+    int stop;                     // BCG_RUN while running
+    int pad_;
+};
+constexpr int BCG_RUN = INT32_MAX;
+constexpr int64_t BCG_MAX_ITERS = (INT32_MAX - 8) / 4;   // iterations a solve's tags can number
+constexpr int bcg_tag(int64_t k, int part) { return (int)(4 * k + part); }
+enum { BCG_PH_INIT = 0, BCG_PH_A = 1, BCG_PH_B = 2, BCG_PH_C = 3 };   // k_bcg_scalar phases
+
 // DCGS2 (delayed classical Gram-Schmidt with re-orthogonalisation, one reduction per Arnoldi
 // step): per-step coefficients produced by the scalar kernel for the update pass
 constexpr int DC_MAXJ = 32;          // restart <= 32 in this mode (4 waves x 8 vectors per lane)
@@ -211,6 +229,8 @@ struct Tuning {
     int line_fuse = 1;        // line path (one rank, canonical rows): the SpMV inside the sweep kernel
     int cyc_ring = 512;       // > 0: cycle-start residual and DCGS2 step 0 through the x-line ring
                               // (k_lsv_ring_epi, ~that many workgroups; 2D line-separable rows)
+    int bcg_fuse = 1;         // BiCGStab with BJ, bs in {1, 2, 4, 8}: phat = M p and shat = M s inside
+                              // k_bcg_p / k_bcg_s (0: the separate apply; the same bits either way)
     int fail_step = -1;       // (test hook) >= 0: this rank's DCGS2 step of that index fails in the
                               // first cycle as a refused launch would (the peer-failure vote, vtk_gmres)
 };
@@ -594,6 +614,28 @@ hipError_t launch_band_check(const int32_t *indptr, const int32_t *indices, int6
                              hipStream_t s);
 
 int vector_grid(int64_t n);
+
+// ---- BiCGStab (vtk_bicgstab.hip) -------------------------------------------------------------
+// every launch: grid workgroups of NT threads (vector_grid), returns at entry once *stop < tag
+// bj usable by the fused forms: block Jacobi, bs in {1, 2, 4, 8} (tridiagonal factors: 2, 4, 8)
+bool bcg_fusable(const BjOp &bj);
+// p = r + beta (p - omega v) with beta, omega from st (first: p = r); bj != null: also phat = M^-1 p
+hipError_t launch_bcg_p(const BicgState *st, int first, int64_t n, const double *r, const double *v, double *p,
+                        const BjOp *bj, double *phat, int grid, const int *stop, int tag, hipStream_t s);
+// s = r - alpha v in place, part = sum s^2; bj != null: also shat = M^-1 s
+hipError_t launch_bcg_s(const BicgState *st, int64_t n, double *r, const double *v, const BjOp *bj, double *shat,
+                        double *part, int grid, const int *stop, int tag, hipStream_t s);
+// omega = reduce(ts) / reduce(tt); x += alpha phat + omega shat; r = s - omega t (in place);
+// part_rr = sum r^2, part_rho = sum rtilde r
+hipError_t launch_bcg_x(const BicgState *st, Red ts, Red tt, int64_t n, double *x, const double *phat,
+                        const double *shat, double *r, const double *t, const double *rtilde, double *part_rr,
+                        double *part_rho, int grid, const int *stop, int tag, hipStream_t s);
+// x += alpha phat, only when *stop == tag (the half-step exit of that iteration fired)
+hipError_t launch_bcg_half_x(const BicgState *st, int64_t n, double *x, const double *phat, int grid, const int *stop,
+                             int tag, hipStream_t s);
+// the scalar step (one workgroup), phase BCG_PH_*; unused quantities: Red{nullptr, 0}
+hipError_t launch_bcg_scalar(int phase, int64_t k, int last, int info_max, double atol, Red q0, Red q1, Red q2, Red q3,
+                             BicgState *st, int *stop_map, const int *stop, int tag, hipStream_t s);
 
 // ---- host helpers (vtk_host.cpp) -------------------------------------------------------------
 void build_tiles(const std::vector<int32_t> &indptr, int align, std::vector<int32_t> &rows,

@@ -9,6 +9,8 @@ the gfx950 kernels of ``libvtkrylov.so`` through the C-ABI in ``include/vtkrylov
     LinearOperator(matvec=block-Jacobi)                      ->  vtkrylov.block_jacobi(A, bs)
     scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=,        ->  vtkrylov.gmres(...)
                               restart=, maxiter=, M=)           (iterative.py:582-841)
+    scipy.sparse.linalg.bicgstab(A, b, x0, rtol=, atol=,     ->  vtkrylov.bicgstab(...)
+                                 maxiter=, M=)                  (one rank; seven work vectors)
 
 Vectors may be NumPy arrays (host; copied in and out) or torch CUDA tensors (device memory,
 used in place).  There is no CPU fallback: without the library or a HIP device every call
@@ -28,7 +30,7 @@ from ._abi import check, lib
 __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "vlasov_operator", "block_jacobi",
            "gmres", "VlasovParams", "vlasov_params", "rhs_splitmix", "partition_rows",
            "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi",
-           "vlasov_line_stride"]
+           "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats"]
 
 VlasovParams = _abi.VlasovParams
 
@@ -817,6 +819,77 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
         if prev is not None:
             A.ctx.set_orth(prev)
     _last_stats = SolveStats(**st.as_dict())
+    return x, info.value
+
+
+@dataclass
+class BicgstabStats:
+    iterations: int    # v = A M p products computed
+    rnorm: float       # true residual ||b - A x|| of the returned x
+    bnorm: float
+    atol_eff: float
+    t_solve: float
+    bytes_moved: float
+    half_step: int     # 1: left through the ||s|| test (SciPy's callback count is iterations - half_step)
+
+
+_last_bicgstab_stats: BicgstabStats | None = None
+
+
+def last_bicgstab_stats() -> BicgstabStats | None:
+    return _last_bicgstab_stats
+
+
+def bicgstab(A, b, x0=None, *, rtol=1e-5, atol=0., maxiter=None, M=None, callback=None):
+    """``scipy.sparse.linalg.bicgstab`` on the GPU (iterative.py, ``bicgstab``: right-preconditioned,
+    SciPy's control flow, breakdown tests and ``info`` convention: 0 converged, -10 / -11 a
+    breakdown, else ``maxiter``).  Returns ``(x, info)``.
+
+    Seven work vectors whatever the problem, no restart parameter.  The reductions are summed in
+    the device's fixed order, not NumPy's: the iterate is deterministic from run to run and agrees
+    with SciPy's to the tolerance, not bit for bit, and the iteration count may differ by a few
+    (INTEGRATION.md).  One rank only: a context with a communicator of more than one rank raises
+    (ERR_STATE).
+
+    ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
+    :class:`BlockJacobi` or a :class:`LineJacobi` built on ``A``; any other preconditioner raises
+    TypeError (no CPU fallback).  ``callback`` is not supported (the loop never returns to the
+    host).  ``maxiter``: None = SciPy's default (10 n); an explicit value must be a positive integer.
+    """
+    global _last_bicgstab_stats
+    if callback is not None:
+        raise NotImplementedError("vtkrylov.bicgstab: callbacks would force a host round trip per "
+                                  "iteration and are not supported")
+    if M is not None and not isinstance(M, (BlockJacobi, LineJacobi)):
+        raise TypeError("vtkrylov.bicgstab: M must be None, vtkrylov.BlockJacobi or vtkrylov.LineJacobi")
+    if atol == "legacy" or atol is None or atol < 0:
+        raise ValueError(f"'scipy.sparse.linalg.bicgstab' called with invalid `atol`={atol}; "
+                         "if set, `atol` must be a real, non-negative number.")
+    if maxiter is not None and (int(maxiter) != maxiter or int(maxiter) <= 0):
+        raise ValueError(f"vtkrylov.bicgstab: maxiter must be a positive integer or None, got {maxiter!r}")
+    if not isinstance(A, CsrOperator):
+        A = csr_matrix(A)
+    n = A.n_local
+    vb = _Vec(b, n)
+    if x0 is None:
+        if vb.kind == _abi.PTR_DEVICE:
+            import torch
+            x = torch.zeros_like(vb.obj)
+        else:
+            x = np.zeros(n)
+    else:
+        if vb.kind == _abi.PTR_DEVICE:
+            x = x0.clone()
+        else:
+            x = np.array(x0, dtype=np.float64, copy=True).reshape(-1)
+    vx = _Vec(x, n, writable=True)
+    x = vx.obj
+    info = C.c_int()
+    st = _abi.BicgstabStats()
+    check(lib().vtk_bicgstab(A.handle, None if M is None else M.handle, vb.ptr, vx.ptr, float(rtol), float(atol),
+                             0 if maxiter is None else int(maxiter), vb.kind, C.byref(info), C.byref(st)),
+          A.ctx.handle)
+    _last_bicgstab_stats = BicgstabStats(**st.as_dict())
     return x, info.value
 
 

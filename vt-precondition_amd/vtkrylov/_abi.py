@@ -49,6 +49,15 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BicgstabStats(C.Structure):
+    _fields_ = [("iterations", C.c_int64), ("rnorm", C.c_double), ("bnorm", C.c_double),
+                ("atol_eff", C.c_double), ("t_solve", C.c_double), ("bytes_moved", C.c_double),
+                ("half_step", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 P = C.c_void_p
 I32P = C.POINTER(C.c_int32)
 I64P = C.POINTER(C.c_int64)
@@ -111,6 +120,8 @@ PROTOTYPES = {
     "vtk_precond_matvec": (C.c_int, [P, P, P, P, C.c_int]),
     "vtk_gmres": (C.c_int, [P, P, P, P, C.c_double, C.c_double, C.c_int, C.c_int64, C.c_int,
                             C.POINTER(C.c_int), C.POINTER(Stats)]),
+    "vtk_bicgstab": (C.c_int, [P, P, P, P, C.c_double, C.c_double, C.c_int64, C.c_int,
+                               C.POINTER(C.c_int), C.POINTER(BicgstabStats)]),
     "vtk_gmres_set_orth": (C.c_int, [P, C.c_int]),
     "vtk_gmres_set_band": (C.c_int, [P, C.c_int]),
     "vtk_bjacobi_create_ex": (C.c_int, [P, C.c_int, C.c_int, C.c_void_p]),

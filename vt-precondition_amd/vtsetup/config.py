@@ -75,6 +75,7 @@ class SolverConfig:
     line_len: int | None = None   # operator/line_len: None (absent / "auto") = detected by vtk_csr_create
     gpus: int = 1                 # run/gpus: ranks, one process per GPU (absent: 1)
     comm: str = "rccl"            # run/comm: rccl, or host (host-staged, ranks may share a GPU)
+    method: str = "gmres"         # solver/method: gmres, or bicgstab (one rank; absent: gmres)
 
     @classmethod
     def load(cls, path: str = DEFAULT_XML, **overrides) -> "SolverConfig":
@@ -103,6 +104,7 @@ class SolverConfig:
         cfg.line_len = None if ll in ("", "auto") else int(ll)
         cfg.gpus = int(t.get_optional("run/gpus", "1") or 1)
         cfg.comm = (t.get_optional("run/comm", "rccl") or "rccl").lower()
+        cfg.method = (t.get_optional("solver/method", "gmres") or "gmres").lower()
         for k, v in overrides.items():
             if v is not None:
                 setattr(cfg, k, v)
@@ -110,10 +112,14 @@ class SolverConfig:
             raise ValueError(f"unknown preconditioner {cfg.preconditioner!r}")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")
+        if cfg.method not in ("gmres", "bicgstab"):
+            raise ValueError(f"unknown solver/method {cfg.method!r} (gmres, bicgstab)")
         if cfg.gpus < 1:
             raise ValueError(f"run/gpus must be >= 1, got {cfg.gpus}")
         if cfg.comm not in ("rccl", "host"):
             raise ValueError(f"unknown run/comm {cfg.comm!r} (rccl, host)")
+        if cfg.method == "bicgstab" and cfg.gpus > 1:
+            raise ValueError(f"solver/method bicgstab runs on one rank; run/gpus is {cfg.gpus} (use gmres across ranks)")
         return cfg
 
     def slab_align(self) -> int:

@@ -8,6 +8,7 @@ vt_precondition.py:66-79.
 
     python -m vtsetup.krylov_precondition [--config C1] [--xml path] [--report out.json]
                                           [--operator-file matrix.npz] [--gpus N] [--comm host]
+                                          [--method bicgstab]
 
 ``run/gpus`` > 1 (or ``--gpus``): ``test_main`` starts one process per rank before anything
 touches a GPU (the torch.distributed.run environment contract: RANK, WORLD_SIZE, MASTER_*);
@@ -104,6 +105,15 @@ class KrylovPrecondition:
         c = self.cfg
         self.b = vk.rhs_splitmix(self.A.n_global, seed=c.seed, r0=self.A.row_begin, r1=self.A.row_end)
         self._barrier()
+        if c.method == "bicgstab":
+            if self.world > 1:
+                raise ValueError("solver/method bicgstab runs on one rank (use gmres across ranks)")
+            self.x, info = vk.bicgstab(self.A, self.b, rtol=c.rtol, atol=c.atol, maxiter=c.maxiter or None, M=self.M)
+            st = vk.last_bicgstab_stats()
+            self.result["solve"] = {"method": "bicgstab", "info": info, "iterations": st.iterations,
+                                    "half_step": st.half_step, "rnorm": st.rnorm, "bnorm": st.bnorm,
+                                    "t_solve_s": st.t_solve}
+            return
         self.x, info = vk.gmres(self.A, self.b, rtol=c.rtol, atol=c.atol, restart=c.restart,
                                 maxiter=c.maxiter or None, M=self.M, orth=c.orth)
         st = vk.last_stats()
@@ -251,6 +261,7 @@ def test_main(argv=None) -> int:
     ap.add_argument("--operator-file", help="SciPy save_npz CSR archive to solve")
     ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "none"])
     ap.add_argument("--orth", choices=["auto", "mgs", "dcgs2"])
+    ap.add_argument("--method", choices=["gmres", "bicgstab"], help="solver (overrides solver/method)")
     ap.add_argument("--gpus", type=int, help="ranks (overrides run/gpus)")
     ap.add_argument("--comm", choices=["rccl", "host"], help="transport (overrides run/comm)")
     ap.add_argument("--x-out", help="write the whole solution (.npy) from rank 0")
@@ -258,7 +269,7 @@ def test_main(argv=None) -> int:
     a = ap.parse_args(argv)
     try:
         cfg = SolverConfig.load(a.xml, config=a.config, report=a.report, operator_file=a.operator_file,
-                                preconditioner=a.preconditioner, orth=a.orth, gpus=a.gpus, comm=a.comm)
+                                preconditioner=a.preconditioner, orth=a.orth, gpus=a.gpus, comm=a.comm, method=a.method)
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
             return _rank_main(cfg, a)
         if cfg.gpus > 1:
