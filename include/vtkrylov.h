@@ -379,9 +379,23 @@ int vtk_gmres_set_band(vtk_ctx *ctx, int on);
  * holds the last completed iterate.  Fixed memory: seven work vectors of n_local doubles,
  * allocated for the call.  Every test and every scalar of the loop stays on the device; the
  * host issues iterations ahead and watches a mapped stop flag, with no synchronisation per
- * iteration.  ONE RANK ONLY: on a context whose communicator has more than one rank the call
- * returns VTK_ERR_STATE (the failure-vote protocol of vtk_gmres would need its own design
- * here).  (additive, ABI 6) */
+ * iteration.  (additive, ABI 6)
+ *
+ * ACROSS RANKS (a context with a communicator, 1-8 ranks): b and x are this rank's rows, as
+ * for vtk_gmres; every rank passes the same rtol, atol and maxiter; a rank without rows takes
+ * part in every collective.  An iteration has two halo exchanges and four all-reduces of a
+ * small record each (the sums a scalar step consumes plus a failure vote); ||b||, the
+ * `x0.any()` flag and the true residual are all-reduced too, so the bnrm2 == 0 shortcut and
+ * the r = b / r = b - A x0 choice are global decisions and info and every field of the
+ * statistics but t_solve are the same on every rank.  Every rank enqueues the same iterations:
+ * the host leaves the loop on the device's stop record alone.
+ * Failure containment, as for vtk_gmres: a rank whose launch fails mid-solve sets a sticky
+ * vote and keeps issuing the same launches and collectives; the first scalar step that reads
+ * a nonzero all-reduced vote stops every rank at the same point, and x is never partly
+ * updated by the iteration in which the vote arrived.  The failing rank returns its own error
+ * (a failed allocation of the work vectors, VTK_ERR_NOMEM, travels in the first all-reduce),
+ * the others VTK_ERR_PEER; the communicator stays usable.  A collective that itself fails
+ * (VTK_ERR_RCCL, or a host hook) returns at once and marks the communicator broken. */
 typedef struct {
     int64_t iterations;    /* v = A M p products computed                          */
     double rnorm;          /* true residual ||b - A x|| of the returned x          */

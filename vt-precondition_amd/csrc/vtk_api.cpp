@@ -2051,7 +2051,8 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
 // scipy.sparse.linalg.bicgstab (iterative.py) with every vector operation, every reduction and
 // every test of the loop on the device (vtk_bicgstab.hip).  The host enqueues whole
 // iterations, LOOKAHEAD of them ahead of the device, and watches the mapped stop flag; kernels
-// tagged after the stop return at entry.  One rank.
+// tagged after the stop return at entry.  Across ranks (vtk_ctx::dist) the sums are all-reduced as
+// small records that carry a failure vote (k_bcg_reduce; DESIGN.md §3j, "Across ranks").
 static_assert(sizeof(BicgState) <= sizeof(GmresState), "the pinned state mirror holds either solver's record");
 
 // bytes per row of M as the standalone apply and the fused k_bcg_p / k_bcg_s read it: the stored
@@ -2073,38 +2074,94 @@ int run_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rto
     maxiter = std::min(maxiter, BCG_MAX_ITERS);
     const int64_t ld = round_up(std::max<int64_t>(n, 1), 64);
     const int G = grid_for(c, vector_grid(n));
-    // work: r (s in place) | rtilde | p | v | t | phat | shat, then the device state
+    const bool dist = c->dist;
+    // partial-sum slots (vtk_ctx::d_part, GMAX each)
+    double *p_vv = c->d_part, *p_rv = c->d_part + GMAX, *p_ss = c->d_part + 2 * GMAX, *p_tt = c->d_part + 3 * GMAX;
+    double *p_ts = c->d_part + 4 * GMAX, *p_rr = c->d_part + 5 * GMAX, *p_rho = c->d_part + 6 * GMAX;
+    double *p_b = c->d_part + 7 * GMAX;
+    const Red none{nullptr, 0};
+    // across ranks: the all-reduced records (BCG_REC_*) and this rank's sticky failure vote
+    double *rec = c->d_scal, *my_vote = &c->d_scal[DC_VOTE + 1];
+    int local_rc = VTK_OK;
+    std::string local_msg;
+    bool fail_pending = c->tune.fail_step >= 0;
+    // A launch of the solve that failed: soft_launch's rule.  One rank: the error returns at once.
+    // Across ranks the peers are already inside the next collective: the rank records its error, sets
+    // its vote and goes on issuing the same launches and collectives; the next scalar step that reads
+    // a nonzero all-reduced vote stops every rank at the same point
+    auto soft = [&](hipError_t e, const char *what) -> int {
+        if (e == hipSuccess) return VTK_OK;
+        const int code = e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP;
+        const std::string msg = std::string(what) + ": " + hipGetErrorString(e);
+        if (!dist) return fail(c, code, msg);
+        if (local_rc == VTK_OK) {
+            local_msg = msg + " (the ranks left the solve together at the next all-reduce)";
+            local_rc = fail(c, code, local_msg);
+            HIPCHK(c, hipMemsetAsync(my_vote, 1, sizeof(double), c->stream));
+        }
+        return VTK_OK;
+    };
+#define BSOFT(x) TRY(soft((x), #x))
+    // the ranks leave together after a nonzero vote: this rank's own error, or VTK_ERR_PEER
+    auto left = [&](const std::string &where) -> int {
+        prof_flush(c);
+        if (local_rc != VTK_OK) return fail(c, local_rc, local_msg);
+        return fail(c, VTK_ERR_PEER, "vtk_bicgstab: a peer rank failed " + where + "; every rank left the solve there");
+    };
+    // rec[0..nq) = this rank's sums of q0.., rec[nq] = its vote (k_bcg_reduce), then summed over the ranks
+    auto gsum = [&](Red q0, Red q1, Red q2, Red q3, int nq, double *dst, const int *stp, int tag) -> int {
+        { Prof pf(c, "bcg_reduce", tag, 8.0 * (q0.cnt + q1.cnt + q2.cnt + q3.cnt));
+          BSOFT(launch_bcg_reduce(q0, q1, q2, q3, nq, my_vote, dst, stp, tag, c->stream)); }
+        Prof pf(c, "allreduce", tag, 8.0 * (nq + 1));
+        return comm_allreduce(c, dst, nq + 1);
+    };
+
+    // work: r (s in place) | rtilde | p | v | t | phat | shat, then the device state.  Across ranks
+    // a failed allocation is voted into the first all-reduce, which every rank is about to enter
     DBuf work;
-    TRY(dalloc(c, work, (7 * (size_t)ld + 16) * sizeof(double)));
+    const int arc = dalloc(c, work, (7 * (size_t)ld + 16) * sizeof(double));
+    if (arc != VTK_OK) {
+        if (!dist) return arc;
+        local_rc = arc;
+        local_msg = c->err;
+    }
+    const double n8 = 8.0 * n;
+
+    // ||b|| and `x.any()`: the host decisions before the loop (bnrm2 == 0, r = b or b - A x), global
+    // across ranks: sum b^2, the flag and the vote travel in one all-reduce
+    { Prof pf(c, "dot", -1, n8);
+      HIPCHK(c, launch_dot(b, nullptr, n, p_b, G, c->stream)); }
+    HIPCHK(c, hipMemsetAsync(&c->d_scal[2], 0, sizeof(double), c->stream));
+    { Prof pf(c, "any", -1, n8);
+      HIPCHK(c, launch_any_nonzero(x, n, &c->d_scal[2], c->stream)); }
+    double h3[3] = {0.0, 0.0, 0.0};
+    double bnrm2;
+    bool r_is_b;
+    if (dist) {
+        HIPCHK(c, hipMemsetAsync(my_vote, local_rc == VTK_OK ? 0 : 1, sizeof(double), c->stream));
+        TRY(gsum(Red{p_b, G}, Red{&c->d_scal[2], 1}, none, none, 2, rec + BCG_REC_PRE, nullptr, -1));
+        HIPCHK(c, hipMemcpyAsync(h3, rec + BCG_REC_PRE, sizeof(h3), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h3[2] != 0.0) return left("before the first iteration");
+        bnrm2 = std::sqrt(h3[0]);
+        r_is_b = h3[1] == 0.0;
+    } else {
+        HIPCHK(c, launch_finalize(Red{p_b, G}, &c->d_scal[0], 1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h3, c->d_scal, sizeof(h3), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        bnrm2 = h3[0];
+        r_is_b = h3[2] == 0.0;
+    }
     double *r = work.as<double>(), *rtilde = r + ld, *p = rtilde + ld, *v = p + ld, *t = v + ld;
     double *phat = M ? t + ld : p, *shat = M ? t + 2 * ld : r;   // no preconditioner: M p = p, M s = s
     BicgState *ds = reinterpret_cast<BicgState *>(r + 7 * (size_t)ld);
     BicgState *hs = reinterpret_cast<BicgState *>(c->h_state);
     const int *stop = &ds->stop;
     volatile int *mirror = c->h_stop;
-    // partial-sum slots (vtk_ctx::d_part, GMAX each)
-    double *p_vv = c->d_part, *p_rv = c->d_part + GMAX, *p_ss = c->d_part + 2 * GMAX, *p_tt = c->d_part + 3 * GMAX;
-    double *p_ts = c->d_part + 4 * GMAX, *p_rr = c->d_part + 5 * GMAX, *p_rho = c->d_part + 6 * GMAX;
-    double *p_b = c->d_part + 7 * GMAX;
-    const Red none{nullptr, 0};
-    const double n8 = 8.0 * n;
     const double b_csr = solver_matrix_bytes(A);
     const double b_inv = bcg_prec_row_bytes(M) * n;
     const BjOp bj = bj_op(M);
     const bool fuse = M && c->tune.bcg_fuse && bcg_fusable(bj);
-
-    // ||b|| and `x.any()`: the one host decision before the loop (bnrm2 == 0, r = b or b - A x)
-    { Prof pf(c, "dot", -1, n8);
-      HIPCHK(c, launch_dot(b, nullptr, n, p_b, G, c->stream)); }
-    HIPCHK(c, launch_finalize(Red{p_b, G}, &c->d_scal[0], 1, c->stream));
-    HIPCHK(c, hipMemsetAsync(&c->d_scal[2], 0, sizeof(double), c->stream));
-    { Prof pf(c, "any", -1, n8);
-      HIPCHK(c, launch_any_nonzero(x, n, &c->d_scal[2], c->stream)); }
-    double h3[3] = {0.0, 0.0, 0.0};
-    HIPCHK(c, hipMemcpyAsync(h3, c->d_scal, sizeof(h3), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const double bnrm2 = h3[0];
-    const bool r_is_b = h3[2] == 0.0;
     atol = std::max(atol, rtol * bnrm2);                    // _get_atol_rtol
     vtk_bicgstab_stats st{};
     st.bnorm = bnrm2;
@@ -2129,7 +2186,7 @@ int run_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rto
         TRY(halo_exchange(A, x));
         Prof pf(c, "spmv_resid", -1, b_csr + 3 * n8);
         const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, x), A);
-        HIPCHK(c, launch_spmv(in, EPI_RESID, r, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream));
+        BSOFT(launch_spmv(in, EPI_RESID, r, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream));
         rr0 = Red{p_rr, spmv_grid(in)};
     }
     HIPCHK(c, hipMemcpyAsync(rtilde, r, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -2137,8 +2194,18 @@ int run_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rto
     hs->stop = BCG_RUN;
     HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(BicgState), hipMemcpyHostToDevice, c->stream));
     *mirror = BCG_RUN;
+    const double *vI = nullptr, *vA = nullptr, *vB = nullptr, *vW = nullptr, *vC = nullptr;
+    if (dist) {   // the initial residual's partials, summed over the ranks
+        TRY(gsum(rr0, none, none, none, 1, rec + BCG_REC_INIT, stop, 0));
+        rr0 = Red{rec + BCG_REC_INIT, 1};
+        vI = rec + BCG_REC_INIT + 1;
+        vA = rec + BCG_REC_A + 1;
+        vB = rec + BCG_REC_B + 1;
+        vW = rec + BCG_REC_W + 2;
+        vC = rec + BCG_REC_C + 2;
+    }
     { Prof pf(c, "bcg_scalar", 0, 8.0 * rr0.cnt);
-      HIPCHK(c, launch_bcg_scalar(BCG_PH_INIT, 0, 0, info_max, atol, rr0, none, none, none, ds, c->d_stop, stop, 0, c->stream)); }
+      BSOFT(launch_bcg_scalar(BCG_PH_INIT, 0, 0, info_max, atol, rr0, none, none, none, vI, ds, c->d_stop, stop, 0, c->stream)); }
 
     hipEvent_t ev[LOOKAHEAD + 1];
     for (auto &e : ev) e = nullptr;
@@ -2150,63 +2217,113 @@ int run_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rto
         TRY(halo_exchange(A, xin));
         Prof pf(c, "spmv_w", tag, b_csr + 3 * n8);
         const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, xin), A);
-        HIPCHK(c, launch_spmv(in, EPI_PREC, y, nullptr, BjOp{}, v0, part0, part1, stop, tag, c->stream));
+        BSOFT(launch_spmv(in, EPI_PREC, y, nullptr, BjOp{}, v0, part0, part1, stop, tag, c->stream));
         cnt = spmv_grid(in);
         return VTK_OK;
     };
     auto apply = [&](const double *in, double *out, int tag) -> int {
         Prof pf(c, prec_cls(M), tag, b_inv + 2 * n8);
-        HIPCHK(c, launch_bj_apply(bj, n, in, out, nullptr, nullptr, nullptr, G, stop, tag, c->stream));
+        BSOFT(launch_bj_apply(bj, n, in, out, nullptr, nullptr, nullptr, G, stop, tag, c->stream));
         return VTK_OK;
     };
+    // Across ranks every sum a scalar step or k_bcg_x consumes is all-reduced first (four collectives
+    // per iteration: A, B, omega, C), each record carrying the vote; every rank then reads the same
+    // bits and computes the same alpha, omega, beta and the same stop
     for (int64_t k = 0; k < maxiter; ++k) {
         const int t1 = bcg_tag(k, 1), t3 = bcg_tag(k, 3);
         const int first = k == 0 ? 1 : 0;
         int cnt = 0;
+        bool refused = false;
+        if (fail_pending && k == c->tune.fail_step) {   // test hook: as if this iteration's first launch were refused
+            fail_pending = false;
+            refused = true;
+            TRY(soft(hipErrorLaunchFailure, "injected failure (tuning fail_step)"));
+        }
         // p = r + beta (p - omega v); phat = M p; v = A phat; rv = <rtilde, v>; alpha
-        { Prof pf(c, "bcg_p", t1, (first ? 2 : 4) * n8 + (fuse ? b_inv + n8 : 0.0));
-          HIPCHK(c, launch_bcg_p(ds, first, n, r, v, p, fuse ? &bj : nullptr, phat, G, stop, t1, c->stream)); }
+        if (!refused) {
+            Prof pf(c, "bcg_p", t1, (first ? 2 : 4) * n8 + (fuse ? b_inv + n8 : 0.0));
+            BSOFT(launch_bcg_p(ds, first, n, r, v, p, fuse ? &bj : nullptr, phat, G, stop, t1, c->stream));
+        }
         if (M && !fuse) TRY(apply(p, phat, t1));
         TRY(product(phat, v, rtilde, p_vv, p_rv, t1, cnt));
-        { Prof pf(c, "bcg_scalar", t1, 8.0 * cnt);
-          HIPCHK(c, launch_bcg_scalar(BCG_PH_A, k, 0, info_max, atol, none, Red{p_rv, cnt}, none, none, ds, c->d_stop, stop, t1, c->stream)); }
+        Red q_rv{p_rv, cnt};
+        if (dist) {
+            TRY(gsum(q_rv, none, none, none, 1, rec + BCG_REC_A, stop, t1));
+            q_rv = Red{rec + BCG_REC_A, 1};
+        }
+        { Prof pf(c, "bcg_scalar", t1, 8.0 * q_rv.cnt);
+          BSOFT(launch_bcg_scalar(BCG_PH_A, k, 0, info_max, atol, none, q_rv, none, none, vA, ds, c->d_stop, stop, t1, c->stream)); }
         // s = r - alpha v (in r); ||s|| < atol: the half-step exit
         { Prof pf(c, "bcg_s", t1, 3 * n8 + (fuse ? b_inv + n8 : 0.0));
-          HIPCHK(c, launch_bcg_s(ds, n, r, v, fuse ? &bj : nullptr, shat, p_ss, G, stop, t1, c->stream)); }
-        { Prof pf(c, "bcg_scalar", t1, 8.0 * G);
-          HIPCHK(c, launch_bcg_scalar(BCG_PH_B, k, 0, info_max, atol, Red{p_ss, G}, none, none, none, ds, c->d_stop, stop, t1, c->stream)); }
+          BSOFT(launch_bcg_s(ds, n, r, v, fuse ? &bj : nullptr, shat, p_ss, G, stop, t1, c->stream)); }
+        Red q_ss{p_ss, G};
+        if (dist) {
+            TRY(gsum(q_ss, none, none, none, 1, rec + BCG_REC_B, stop, t1));
+            q_ss = Red{rec + BCG_REC_B, 1};
+        }
+        { Prof pf(c, "bcg_scalar", t1, 8.0 * q_ss.cnt);
+          BSOFT(launch_bcg_scalar(BCG_PH_B, k, 0, info_max, atol, q_ss, none, none, none, vB, ds, c->d_stop, stop, t1, c->stream)); }
         // shat = M s; t = A shat; omega = <t, s> / <t, t>; x += alpha phat + omega shat; r = s - omega t
         if (M && !fuse) TRY(apply(r, shat, t3));
         TRY(product(shat, t, r, p_tt, p_ts, t3, cnt));
-        { Prof pf(c, "bcg_x", t3, 8 * n8 + 16.0 * cnt);
-          HIPCHK(c, launch_bcg_x(ds, Red{p_ts, cnt}, Red{p_tt, cnt}, n, x, phat, shat, r, t, rtilde, p_rr, p_rho, G, stop, t3, c->stream)); }
-        { Prof pf(c, "bcg_scalar", t3, 16.0 * cnt + 16.0 * G);
-          HIPCHK(c, launch_bcg_scalar(BCG_PH_C, k, k + 1 == maxiter ? 1 : 0, info_max, atol, Red{p_ts, cnt}, Red{p_tt, cnt},
-                                      Red{p_rr, G}, Red{p_rho, G}, ds, c->d_stop, stop, t3, c->stream)); }
+        Red q_ts{p_ts, cnt}, q_tt{p_tt, cnt}, q_rr{p_rr, G}, q_rho{p_rho, G};
+        if (dist) {
+            TRY(gsum(q_ts, q_tt, none, none, 2, rec + BCG_REC_W, stop, t3));
+            q_ts = Red{rec + BCG_REC_W, 1};
+            q_tt = Red{rec + BCG_REC_W + 1, 1};
+        }
+        { Prof pf(c, "bcg_x", t3, 8 * n8 + 8.0 * (q_ts.cnt + q_tt.cnt));
+          BSOFT(launch_bcg_x(ds, q_ts, q_tt, n, x, phat, shat, r, t, rtilde, p_rr, p_rho, vW, G, stop, t3, c->stream)); }
+        if (dist) {
+            TRY(gsum(q_rr, q_rho, none, none, 2, rec + BCG_REC_C, stop, t3));
+            q_rr = Red{rec + BCG_REC_C, 1};
+            q_rho = Red{rec + BCG_REC_C + 1, 1};
+        }
+        { Prof pf(c, "bcg_scalar", t3, 8.0 * (q_ts.cnt + q_tt.cnt + q_rr.cnt + q_rho.cnt));
+          BSOFT(launch_bcg_scalar(BCG_PH_C, k, k + 1 == maxiter ? 1 : 0, info_max, atol, q_ts, q_tt, q_rr, q_rho, vC, ds,
+                                  c->d_stop, stop, t3, c->stream)); }
         HIPCHK(c, hipEventRecord(ev[k % (LOOKAHEAD + 1)], c->stream));
         if (k >= LOOKAHEAD) {
             HIPCHK(c, hipEventSynchronize(ev[(k - LOOKAHEAD) % (LOOKAHEAD + 1)]));
-            if (*mirror != BCG_RUN) break;
+            // across ranks the test is a function of device state alone (the GMRES loop's comparison):
+            // a stop of an iteration up to k - LOOKAHEAD, so every rank enqueues the same iterations
+            // and the same collectives; one rank: whatever the mirror shows by now
+            if (dist ? *mirror <= bcg_tag(k - LOOKAHEAD, 3) : *mirror != BCG_RUN) break;
         }
     }
     HIPCHK(c, hipMemcpyAsync(hs, ds, sizeof(BicgState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (hs->stop == BCG_RUN) return fail(c, VTK_ERR_HIP, "vtk_bicgstab: the loop ended without a stop record");
+    if (hs->stop == BCG_RUN) {   // (across ranks: voted into the last all-reduce, which the peers enter)
+        if (!dist) return fail(c, VTK_ERR_HIP, "vtk_bicgstab: the loop ended without a stop record");
+        TRY(soft(hipErrorLaunchFailure, "vtk_bicgstab: the loop ended without a stop record"));
+    }
     const int64_t its = hs->iterations;
     if (hs->half_step) {   // x += alpha phat: the flag sits at that iteration's half-step tag
         Prof pf(c, "bcg_x", -1, 3 * n8);
-        HIPCHK(c, launch_bcg_half_x(ds, n, x, phat, G, stop, bcg_tag(its - 1, 2), c->stream));
+        BSOFT(launch_bcg_half_x(ds, n, x, phat, G, stop, bcg_tag(its - 1, 2), c->stream));
     }
-    // the true residual of the returned x (t is free now)
+    // the true residual of the returned x (t is free now); across ranks its all-reduce carries the
+    // last vote: a failure after the stop record still reaches every rank
     {
         TRY(halo_exchange(A, x));
         const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, x), A);
         { Prof pf(c, "spmv_resid", -1, b_csr + 3 * n8);
-          HIPCHK(c, launch_spmv(in, EPI_RESID, t, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream)); }
-        HIPCHK(c, launch_finalize(Red{p_rr, spmv_grid(in)}, &c->d_scal[1], 1, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&st.rnorm, &c->d_scal[1], sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+          BSOFT(launch_spmv(in, EPI_RESID, t, b, BjOp{}, nullptr, p_rr, nullptr, nullptr, 0, c->stream)); }
+        if (dist) {
+            double h2[2] = {0.0, 0.0};
+            TRY(gsum(Red{p_rr, spmv_grid(in)}, none, none, none, 1, rec + BCG_REC_FIN, nullptr, -1));
+            HIPCHK(c, hipMemcpyAsync(h2, rec + BCG_REC_FIN, sizeof(h2), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (h2[1] != 0.0)
+                return left(hs->peer_failed ? "in iteration " + std::to_string(its) : std::string("after the last iteration"));
+            st.rnorm = std::sqrt(h2[0]);
+        } else {
+            HIPCHK(c, launch_finalize(Red{p_rr, spmv_grid(in)}, &c->d_scal[1], 1, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&st.rnorm, &c->d_scal[1], sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
     }
+#undef BSOFT
     if (c->prof_on) prof_flush(c, hs->stop);
     st.iterations = its;
     st.half_step = hs->half_step;
@@ -3014,9 +3131,6 @@ int vtk_bicgstab(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rto
     if (M && M->A != A) return fail(c, VTK_ERR_ARG, "vtk_bicgstab: preconditioner built for another operator");
     TRY(prec_usable(M, "vtk_bicgstab"));
     if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail(c, VTK_ERR_ARG, "vtk_bicgstab: tolerances must be non-negative");
-    if (c->world > 1)
-        return fail(c, VTK_ERR_STATE, "vtk_bicgstab: one rank only (this context's communicator has " +
-                                          std::to_string(c->world) + " ranks); use vtk_gmres across ranks");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = A->n_local;
     Staged sb, sx;

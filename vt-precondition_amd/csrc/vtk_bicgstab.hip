@@ -1,7 +1,8 @@
 // vtk_bicgstab.hip — gfx950 kernels of the BiCGStab solver (vtk_bicgstab): the
 // solver's own vector updates, their BJ-fused forms and the single-workgroup scalar step.  The two
 // products of an iteration are launch_spmv (vtk_kernels.hip), the unfused preconditioner apply
-// launch_bj_apply.
+// launch_bj_apply.  Across ranks k_bcg_reduce turns the partials a scalar step or k_bcg_x consumes
+// into a small record (the sums and this rank's failure vote) that the driver all-reduces.
 //
 // Conventions of vtk_kernels.hip: fixed grid vector_grid(n) <= GMAX, one partial per workgroup and
 // quantity (no float atomics), wave sums by DPP (block_sum), and every kernel returns at entry once
@@ -105,15 +106,20 @@ __global__ __launch_bounds__(NT) void k_bcg_s(const BicgState *st, int64_t n, do
 }
 
 // omega = <t, s> / <t, t> from the second product's partials (every workgroup sums them in the
-// same fixed order, as k_bcg_scalar does after this kernel); x += alpha phat; x += omega shat;
+// same fixed order, as k_bcg_scalar does after this kernel; across ranks: the two all-reduced sums
+// of the omega record, and its vote); x += alpha phat; x += omega shat;
 // r = s - omega t (s is r's buffer); part_rr = sum r^2, part_rho = sum rtilde r -- the next
 // iteration's rho.  phat / shat may be p / s themselves (no preconditioner): no restrict on them
 __global__ __launch_bounds__(NT) void k_bcg_x(const BicgState *st, Red ts, Red tt, int64_t n, double *x,
                                               const double *phat, const double *shat, double *r,
                                               const double *__restrict__ t, const double *__restrict__ rtilde,
-                                              double *part_rr, double *part_rho, const int *stop, int tag) {
+                                              double *part_rr, double *part_rho, const double *vote, const int *stop,
+                                              int tag) {
     __shared__ double red[NT / 64];
     if (stopped(stop, tag)) return;
+    // across ranks: a rank voted failure in the omega all-reduce -- x and r stay as they are on every
+    // rank (uniform: the record holds the same bits everywhere); scalar step C then lowers the flag
+    if (vote != nullptr && *vote != 0.0) return;
     const double alpha = st->alpha;
     const double nts = reduce_red(ts, red);
     const double ntt = reduce_red(tt, red);
@@ -155,9 +161,10 @@ __global__ __launch_bounds__(NT) void k_bcg_half_x(const BicgState *st, int64_t 
 //   C     q0 = <t, s>, q1 = <t, t>, q2 = sum r^2, q3 = <rtilde, r>: omega, then the top tests of
 //         iteration k + 1 and its beta; last: the loop is exhausted instead, info = maxiter
 // A stop lowers st->stop below every later tag and writes it through to the mapped host mirror.
+// vote (across ranks): the failure-vote slot of the all-reduced record the q* come from.
 __global__ __launch_bounds__(NT) void k_bcg_scalar(int phase, int64_t k, int last, int info_max, double atol, Red q0,
-                                                   Red q1, Red q2, Red q3, BicgState *st, int *stop_map,
-                                                   const int *stop, int tag) {
+                                                   Red q1, Red q2, Red q3, const double *vote, BicgState *st,
+                                                   int *stop_map, const int *stop, int tag) {
     __shared__ double red[NT / 64];
     if (stopped(stop, tag)) return;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -184,6 +191,17 @@ __global__ __launch_bounds__(NT) void k_bcg_scalar(int phase, int64_t k, int las
             st->beta = (rho_new / st->rho_prev) * (st->alpha / st->omega);
         }
     };
+    // across ranks (q* all-reduced): a rank voted failure in this step's all-reduce -- every rank
+    // reads the same sum, so every rank stops here, below each later tag of this iteration and
+    // below the half-step tag (no x update follows); the host returns the error
+    if (vote != nullptr && *vote != 0.0) {
+        st->peer_failed = 1;
+        const int at = phase == BCG_PH_INIT ? 0
+                       : phase == BCG_PH_A  ? bcg_tag(k, 0)
+                       : phase == BCG_PH_B  ? bcg_tag(k, 1)
+                                            : bcg_tag(k, 3);
+        return leave(0, k, at);
+    }
     if (phase == BCG_PH_INIT) {
         st->rnorm = __builtin_sqrt(s0);
         top(0, s0, 0);
@@ -204,6 +222,26 @@ __global__ __launch_bounds__(NT) void k_bcg_scalar(int phase, int64_t k, int las
         if (last) return leave(info_max, k + 1, bcg_tag(k, 3));
         top(k + 1, s3, bcg_tag(k, 3));
     }
+}
+
+// Across ranks: this rank's partial sums of up to four quantities -> rec[0..nq), and this rank's
+// sticky failure vote -> rec[nq]; the driver all-reduces rec (nq + 1 doubles) and the consumers read
+// Red{rec + i, 1}.  One workgroup, the fixed slot order of reduce_red.
+__global__ __launch_bounds__(NT) void k_bcg_reduce(Red q0, Red q1, Red q2, Red q3, int nq, const double *my_vote,
+                                                   double *rec, const int *stop, int tag) {
+    __shared__ double red[NT / 64];
+    if (stopped(stop, tag)) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (nq > 0) s0 = reduce_red(q0, red);
+    if (nq > 1) s1 = reduce_red(q1, red);
+    if (nq > 2) s2 = reduce_red(q2, red);
+    if (nq > 3) s3 = reduce_red(q3, red);
+    if (threadIdx.x != 0) return;
+    if (nq > 0) rec[0] = s0;
+    if (nq > 1) rec[1] = s1;
+    if (nq > 2) rec[2] = s2;
+    if (nq > 3) rec[3] = s3;
+    rec[nq] = *my_vote;
 }
 
 // ---- launchers ----------------------------------------------------------------------------------
@@ -264,9 +302,9 @@ hipError_t launch_bcg_s(const BicgState *st, int64_t n, double *r, const double 
 
 hipError_t launch_bcg_x(const BicgState *st, Red ts, Red tt, int64_t n, double *x, const double *phat,
                         const double *shat, double *r, const double *t, const double *rtilde, double *part_rr,
-                        double *part_rho, int grid, const int *stop, int tag, hipStream_t s) {
+                        double *part_rho, const double *vote, int grid, const int *stop, int tag, hipStream_t s) {
     hipLaunchKernelGGL(k_bcg_x, dim3(grid), dim3(NT), 0, s, st, ts, tt, n, x, phat, shat, r, t, rtilde, part_rr,
-                       part_rho, stop, tag);
+                       part_rho, vote, stop, tag);
     return hipGetLastError();
 }
 
@@ -277,9 +315,17 @@ hipError_t launch_bcg_half_x(const BicgState *st, int64_t n, double *x, const do
 }
 
 hipError_t launch_bcg_scalar(int phase, int64_t k, int last, int info_max, double atol, Red q0, Red q1, Red q2, Red q3,
-                             BicgState *st, int *stop_map, const int *stop, int tag, hipStream_t s) {
-    hipLaunchKernelGGL(k_bcg_scalar, dim3(1), dim3(NT), 0, s, phase, k, last, info_max, atol, q0, q1, q2, q3, st,
-                       stop_map, stop, tag);
+                             const double *vote, BicgState *st, int *stop_map, const int *stop, int tag,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(k_bcg_scalar, dim3(1), dim3(NT), 0, s, phase, k, last, info_max, atol, q0, q1, q2, q3, vote,
+                       st, stop_map, stop, tag);
+    return hipGetLastError();
+}
+
+hipError_t launch_bcg_reduce(Red q0, Red q1, Red q2, Red q3, int nq, const double *my_vote, double *rec,
+                             const int *stop, int tag, hipStream_t s) {
+    if (nq < 0 || nq > 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bcg_reduce, dim3(1), dim3(NT), 0, s, q0, q1, q2, q3, nq, my_vote, rec, stop, tag);
     return hipGetLastError();
 }
 

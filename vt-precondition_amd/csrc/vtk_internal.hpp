@@ -46,8 +46,13 @@ struct BicgState {
     int info;                     // SciPy's return code once stopped
     int half_step;                // left through the ||s|| test
     int stop;                     // BCG_RUN while running
-    int pad_;
+    int peer_failed;              // across ranks: an all-reduced failure vote stopped the solve
 };
+// all-reduced records of the rank path (vtk_ctx::d_scal; the quantities, then the failure vote):
+// the pre-loop record | INIT | A | B | omega | C | the true residual; this rank's own sticky vote
+// sits at d_scal[DC_VOTE + 1] as in vtk_gmres
+enum { BCG_REC_PRE = 8, BCG_REC_INIT = 12, BCG_REC_A = 16, BCG_REC_B = 20, BCG_REC_W = 24, BCG_REC_C = 28,
+       BCG_REC_FIN = 32 };
 constexpr int BCG_RUN = INT32_MAX;
 constexpr int64_t BCG_MAX_ITERS = (INT32_MAX - 8) / 4;   // iterations a solve's tags can number
 constexpr int bcg_tag(int64_t k, int part) { return (int)(4 * k + part); }
@@ -232,7 +237,8 @@ struct Tuning {
     int bcg_fuse = 1;         // BiCGStab with BJ, bs in {1, 2, 4, 8}: phat = M p and shat = M s inside
                               // k_bcg_p / k_bcg_s (0: the separate apply; the same bits either way)
     int fail_step = -1;       // (test hook) >= 0: this rank's DCGS2 step of that index fails in the
-                              // first cycle as a refused launch would (the peer-failure vote, vtk_gmres)
+                              // first cycle as a refused launch would (the peer-failure vote, vtk_gmres);
+                              // vtk_bicgstab: the first launch of that loop index is refused
 };
 }  // namespace vtk
 
@@ -626,16 +632,24 @@ hipError_t launch_bcg_p(const BicgState *st, int first, int64_t n, const double 
 hipError_t launch_bcg_s(const BicgState *st, int64_t n, double *r, const double *v, const BjOp *bj, double *shat,
                         double *part, int grid, const int *stop, int tag, hipStream_t s);
 // omega = reduce(ts) / reduce(tt); x += alpha phat + omega shat; r = s - omega t (in place);
-// part_rr = sum r^2, part_rho = sum rtilde r
+// part_rr = sum r^2, part_rho = sum rtilde r.  vote != null (across ranks): the vote slot of the
+// omega record; nonzero: the kernel returns with x and r untouched
 hipError_t launch_bcg_x(const BicgState *st, Red ts, Red tt, int64_t n, double *x, const double *phat,
                         const double *shat, double *r, const double *t, const double *rtilde, double *part_rr,
-                        double *part_rho, int grid, const int *stop, int tag, hipStream_t s);
+                        double *part_rho, const double *vote, int grid, const int *stop, int tag, hipStream_t s);
 // x += alpha phat, only when *stop == tag (the half-step exit of that iteration fired)
 hipError_t launch_bcg_half_x(const BicgState *st, int64_t n, double *x, const double *phat, int grid, const int *stop,
                              int tag, hipStream_t s);
-// the scalar step (one workgroup), phase BCG_PH_*; unused quantities: Red{nullptr, 0}
+// the scalar step (one workgroup), phase BCG_PH_*; unused quantities: Red{nullptr, 0}.  vote != null
+// (across ranks): the vote slot of the record the quantities come from; nonzero: BicgState::peer_failed
+// and a stop at this step
 hipError_t launch_bcg_scalar(int phase, int64_t k, int last, int info_max, double atol, Red q0, Red q1, Red q2, Red q3,
-                             BicgState *st, int *stop_map, const int *stop, int tag, hipStream_t s);
+                             const double *vote, BicgState *st, int *stop_map, const int *stop, int tag,
+                             hipStream_t s);
+// across ranks (one workgroup): rec[i] = reduce(q_i) for i < nq <= 4, rec[nq] = *my_vote; the driver
+// all-reduces rec[0..nq]
+hipError_t launch_bcg_reduce(Red q0, Red q1, Red q2, Red q3, int nq, const double *my_vote, double *rec,
+                             const int *stop, int tag, hipStream_t s);
 
 // ---- host helpers (vtk_host.cpp) -------------------------------------------------------------
 void build_tiles(const std::vector<int32_t> &indptr, int align, std::vector<int32_t> &rows,

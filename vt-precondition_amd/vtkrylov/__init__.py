@@ -10,7 +10,7 @@ the gfx950 kernels of ``libvtkrylov.so`` through the C-ABI in ``include/vtkrylov
     scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=,        ->  vtkrylov.gmres(...)
                               restart=, maxiter=, M=)           (iterative.py:582-841)
     scipy.sparse.linalg.bicgstab(A, b, x0, rtol=, atol=,     ->  vtkrylov.bicgstab(...)
-                                 maxiter=, M=)                  (one rank; seven work vectors)
+                                 maxiter=, M=)                  (seven work vectors; 1-8 ranks)
 
 Vectors may be NumPy arrays (host; copied in and out) or torch CUDA tensors (device memory,
 used in place).  There is no CPU fallback: without the library or a HIP device every call
@@ -848,8 +848,14 @@ def bicgstab(A, b, x0=None, *, rtol=1e-5, atol=0., maxiter=None, M=None, callbac
     Seven work vectors whatever the problem, no restart parameter.  The reductions are summed in
     the device's fixed order, not NumPy's: the iterate is deterministic from run to run and agrees
     with SciPy's to the tolerance, not bit for bit, and the iteration count may differ by a few
-    (INTEGRATION.md).  One rank only: a context with a communicator of more than one rank raises
-    (ERR_STATE).
+    (INTEGRATION.md).
+
+    Across ranks (a context with a communicator): ``b``, ``x0`` and the returned ``x`` are this
+    rank's rows, as for :func:`gmres`; every rank calls with the same tolerances and ``maxiter``.
+    The sums of an iteration are all-reduced (four small collectives per iteration), so ``info``
+    and every field of :func:`last_bicgstab_stats` but the timing are the same on every rank.  A
+    rank whose launch fails mid-solve raises its own error and the others raise ERR_PEER at the
+    same point; the communicator stays usable.
 
     ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
     :class:`BlockJacobi` or a :class:`LineJacobi` built on ``A``; any other preconditioner raises
