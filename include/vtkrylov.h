@@ -179,6 +179,9 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
  * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
  * band_opt bit 5, odd band steps walking their line ranges the other way round, at every size;
+ * band_opt bit 6 (64), the band step and step 0 of its cycle without the read of the operator's
+ * diagonal: w = p + M^-1 (A - M) p, valid because the band step runs only with the tridiagonal
+ * block-Jacobi factors of the operator's current values -- last-bit differences in w, default on;
  * bcg_fuse: vtk_bicgstab forms phat = M p and shat = M s inside its vector kernels for block Jacobi
  * with bs in {1, 2, 4, 8} -- 0: the separate apply, the same bits) */
 int vtk_ctx_set_tuning(vtk_ctx *ctx, const char *key, int value);

@@ -31,8 +31,8 @@ CLASSES = {   # bench/profile class -> demangled-name prefix (regex) in rocprofv
               # path: SELL-64 layout, tridiagonal-factor BJ(8), DCGS2; fp64 or fp32 values)
     "band_step": r"void vtk::k_band_step<",
     # k_g4_ring<VT, HALO, RL, MODE, GR>: MODE 0 split step, 2 with step 0's dots, 3 the
-    # cycle-start residual; k_lsv_ring_epi<EPI>: 3 residual + BJ, 4 step 0 with its dots
-    "spmv_bj_dc": r"void vtk::k_(sell<(double|float), false, 4, 8, true,|g4_ring<(double|float), (false|true), \d+, 2, \d+>|lsv_ring_epi<4>)",
+    # cycle-start residual; k_lsv_ring_epi<EPI>: 3 residual + BJ, 4 step 0 with its dots (5: without the read of D)
+    "spmv_bj_dc": r"void vtk::k_(sell<(double|float), false, 4, 8, true,|g4_ring<(double|float), (false|true), \d+, 2, \d+>|lsv_ring_epi<[45]>)",
     "spmv": r"void vtk::k_sell<(double|float), false, 0, 1, false,",
     "spmv_bj": r"void vtk::k_(sell<(double|float), false, 2, 8, true,|g4_ring<(double|float), (false|true), \d+, 0, \d+>)",
     "spmv_resid_bj": r"void vtk::k_(sell<(double|float), false, 3, 8, true,|g4_ring<(double|float), (false|true), \d+, 3, \d+>|lsv_ring_epi<3>)",

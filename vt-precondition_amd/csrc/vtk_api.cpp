@@ -1468,13 +1468,16 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
     // median ms per solve (spread of the eight bit-5-off solves): C3 36.62 vs 37.37 (0.18), C3/2
     // slab 18.86 vs 18.95 (0.02), C2 10.21 vs 10.28 (0.08), C3/8 slab 6.16 vs 6.23 (0.04)
     // (profiles/serpentine_ab*.json)
+    // bit 6 (no read of the diagonal table, w = p + M^-1 (A - M) p) exists for the same
+    // instantiations only: masked off with the others where the rows are not canonical line-separable
     const int band_opt = band_lsv && s.A->lsv_canon && band_canon
                              ? (n >= c->tune.band_long_rows ? c->tune.band_opt : c->tune.band_opt & ~(8 | 16))
                              : 0;
     // the band step's matrix bytes: SELL codes + dictionary + (values: 8 B per row from D, or
-    // the SELL values)
+    // the SELL values); with bit 6 no matrix bytes per row at all
+    const bool band_nd = (band_opt & 64) != 0;
     const double b_band = band_lsv ? (s.A->lsv_canon && band_canon
-                                          ? 8.0 * (double)n   // the diagonal only
+                                          ? (band_nd ? 0.0 : 8.0 * (double)n)   // the diagonal only
                                           : b_csr - 8.0 * (double)s.A->sell.entries + 8.0 * (double)n)
                                    : b_csr;
     bool broke = false;
@@ -1495,10 +1498,12 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
         } else if (fused && band && j == 0 && cyc_ring_ok(c, s.A, s.M, true)) {
             // step 0 of a band cycle through the x-line ring (x = v_0; the j = 0 dots only);
             // across ranks the two halo lines first (12.8 KB at C3)
+            // band_nd: the same operator expression as the band steps, no read of D (the guard at the
+            // band step's launch below holds here too: cyc_ring_ok asked bj_op(M).tri)
             TRY(halo_exchange(s.A, pj));
-            Prof pf(c, "spmv_bj_dc", j, b_step);
+            Prof pf(c, "spmv_bj_dc", j, b_step - (band_nd ? n8 : 0.0));
             const bool hl = s.A->band_ghost;
-            SOFT(launch_lsv_ring_epi(EPI_PREC_DC, s.A->d_lsv, pj, nullptr, s.M->d_tri + s.M->tri_ld, s.w, nullptr,
+            SOFT(launch_lsv_ring_epi(band_nd ? EPI_PREC_DC_ND : EPI_PREC_DC, s.A->d_lsv, pj, nullptr, s.M->d_tri + s.M->tri_ld, s.w, nullptr,
                                           nullptr, s.dcpart, n, (int)s.A->band_L, c->tune.cyc_ring, stop, j, &cnt,
                                           c->stream, hl ? s.A->d_halo : nullptr, s.A->band_lblk, s.A->band_xord));
         } else if (fused && bj_split(s.M)) {
@@ -1680,6 +1685,10 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
             a.xord = s.A->band_xord;
             a.lsv = band_lsv ? s.A->d_lsv : nullptr;
             a.canon = band_lsv && s.A->lsv_canon && band_canon ? 2 : 0;   // 2: the straight-line SpMV per line order
+            // bit 6 computes w = p + M^-1 (A - M) p, which is M^-1 A p only while a.mtri holds the
+            // factors of A's CURRENT diagonal blocks.  s.band requires bj_op(M).tri, which is null
+            // unless M->epoch == A->values_epoch (a lagged M takes the non-band path).  A change that
+            // lets a lagged M reach this launch must clear bit 6 here, or the operator is wrong
             a.opt = band_opt;
             SOFT(launch_band_step(a, s.band_grid(j, a.opt), s.A->sell.uniform_w, c->stream));
         } else {

@@ -93,6 +93,15 @@ template <int OPT> __device__ __forceinline__ void band_sync() {
 // blocks' minimum, five: round 6), the 8-row BJ blocks lane-aligned, the v-halo rows at tid
 // BAND_OFF - 1 and BAND_OFF + LP (LP + 2 BAND_OFF <= BAND_T)
 constexpr int BAND_OFF = 16;
+// OPT bit 6 (ND, canonical rows): no read of the diagonal table D.  The band step runs only with the
+// tridiagonal BJ(8) factors of A's current diagonal blocks (bj_op() hands out tri for the operator's
+// current values_epoch only; the launch site in vtk_api.cpp states the guard), so A = M + C with C
+// the x +- 1 couplings and the v +- 1 couplings that cross an 8-row block edge, and
+//   w = M^-1 A p = p + M^-1 (C p):
+// the row sum y = C p skips the diagonal and the in-block v +- 1 products (the in-block couplings
+// still enter bj_trim_group as sub / sup, from the per-line constants), z = M^-1 y, w = p + z.  One
+// 8-B stream per row fewer (load, SPF operand, L2PF row); w differs from the D form in its last bits
+// only, within the DCGS2 bars
 static_assert(BAND_LP + 2 * BAND_OFF <= BAND_T && BAND_OFF % 8 == 0, "band geometry");
 template <int WU, int J, int VMODE = 0, bool GH = true, int OPT = 0>
 __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe<OPT>()))) void k_band_step(BandK a) {
@@ -120,6 +129,7 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
     const bool own = tid >= BAND_OFF && tid < BAND_OFF + LP;
     const bool upd = tid >= BAND_OFF - 1 && tid <= LP + BAND_OFF && v >= 0 && v < L;   // owned rows and the v-halo rows
     constexpr bool LSV = VMODE >= 1, CANON = VMODE == 2;
+    constexpr bool ND = CANON && (OPT & 64);
     const int ii = lane & 7;
     // LSV: the lane's x-coupling values (position v in every line)
     double tx0 = 0.0, tx1 = 0.0;
@@ -196,7 +206,7 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                 const int xs = spmv_line(it);
                 const int64_t rs = (int64_t)xs * L + (own ? v : v0);
                 if (own) {
-                    o.drow = __builtin_nontemporal_load(a.lsv + rs);
+                    if constexpr (!ND) o.drow = __builtin_nontemporal_load(a.lsv + rs);
                     o.mrow = __builtin_nontemporal_load(a.mtri + rs);
                 }
                 o.tv0 = a.lsv[a.n + 2 * L + xs];
@@ -278,7 +288,8 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
     // L2PF: touch the rows iteration itp reads (its line's rows v0 - 1 .. v0 + LP of the J basis
     // vectors, w_j and w_{j-1} (v_0 at j = 0); D and m of its SpMV line), 128-B segments, the
     // rows spread over the waves.  Ghost lines (a neighbour rank's) come from the ghost buffer: skipped
-    constexpr int PF_ROWS = J + 2 + (CANON ? 2 : 0);
+    // (ND: m only)
+    constexpr int PF_ROWS = J + 2 + (CANON ? (ND ? 1 : 2) : 0);
     auto l2_prefetch = [&](int itp) {
         if constexpr ((OPT & 8) != 0) {
             if (itp > nl + 1) return;
@@ -300,7 +311,7 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                     r1 = (int64_t)y * L + vhi;
                 } else {
                     if (itp < 2) continue;
-                    vec = r == J + 2 ? a.lsv : a.mtri;
+                    vec = (r == J + 2 && !ND) ? a.lsv : a.mtri;
                     r0 = (int64_t)xs * L + v0;
                     r1 = r0 + LP;
                 }
@@ -337,7 +348,9 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                 dv = (lane < 32 && qd >= 0 && qd * 64 < a.n) ? a.dict[qd * 16 + (lane & 15)] : 0;
             }
             if constexpr (LSV) {
-                if (own) drow = __builtin_nontemporal_load(a.lsv + row);
+                if constexpr (!ND) {
+                    if (own) drow = __builtin_nontemporal_load(a.lsv + row);
+                }
                 tv0 = a.lsv[a.n + 2 * L + x];
                 tv1 = a.lsv[a.n + 2 * L + X + x];
             } else {
@@ -368,6 +381,7 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
         if (work) {
             // 2. w = M^-1 A p_{j+1} on the part's rows of line x, gathers from the ring
             double sacc = 0.0, sub = 0.0, sup = 0.0;
+            double pc = 0.0;   // ND: p on the lane's row
             if constexpr (CANON) {
                 // the line's stored order of the five kinds (the same for every lane of the line)
                 int64_t cxm, cxp;
@@ -386,12 +400,32 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                     const int vv = own ? v : v0;
                     const double t0 = tx0 * ring[((x - xa) & 3) * BAND_RS - v0 + BAND_OFF + vv];
                     const double t4 = tx1 * ring[((x - xa + 2) & 3) * BAND_RS - v0 + BAND_OFF + vv];
-                    const double t2 = drow * ring[sx + vv];
+                    pc = ring[sx + vv];
+                    const double t2 = drow * pc;
                     const double t1 = tv0 * ring[sx + vv - 1];
                     const double t3 = tv1 * ring[sx + vv + 1];
                     const bool h1 = vv > 0, h3 = vv < L - 1;
                     double sa = 0.0;
-                    if (ord == P_MID) {
+                    if constexpr (ND) {
+                        // y = C p: the v -+ 1 terms only across a block edge, no diagonal term
+                        const bool c1 = h1 && ii == 0, c3 = h3 && ii == 7;
+                        if (ord == P_MID) {
+                            sa = sa + t0;
+                            sa = c1 ? sa + t1 : sa;
+                            sa = c3 ? sa + t3 : sa;
+                            sa = sa + t4;
+                        } else if (ord == P_FIRST) {
+                            sa = c1 ? sa + t1 : sa;
+                            sa = c3 ? sa + t3 : sa;
+                            sa = sa + t4;
+                            sa = sa + t0;
+                        } else {
+                            sa = sa + t4;
+                            sa = sa + t0;
+                            sa = c1 ? sa + t1 : sa;
+                            sa = c3 ? sa + t3 : sa;
+                        }
+                    } else if (ord == P_MID) {
                         sa = sa + t0;
                         sa = h1 ? sa + t1 : sa;
                         sa = sa + t2;
@@ -420,14 +454,16 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                     if (!sl && own) {
                         if (kind == 0) sacc += tx0 * ring[((x - xa) & 3) * BAND_RS - v0 + BAND_OFF + v];
                         else if (kind == 4) sacc += tx1 * ring[((x - xa + 2) & 3) * BAND_RS - v0 + BAND_OFF + v];
-                        else if (kind == 2) sacc += drow * ring[sx + v];
-                        else if (kind == 1) {
+                        else if (kind == 2) {
+                            if constexpr (ND) pc = ring[sx + v];
+                            else sacc += drow * ring[sx + v];
+                        } else if (kind == 1) {
                             if (v > 0) {
-                                sacc += tv0 * ring[sx + v - 1];
+                                if (!ND || ii == 0) sacc += tv0 * ring[sx + v - 1];
                                 if (ii > 0) sub = sub + tv0;
                             }
                         } else if (v < L - 1) {
-                            sacc += tv1 * ring[sx + v + 1];
+                            if (!ND || ii == 7) sacc += tv1 * ring[sx + v + 1];
                             if (ii < 7) sup = sup + tv1;
                         }
                     }
@@ -463,7 +499,8 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
                     }
                 }
             }
-            const double z = bj_trim_group<8>(own ? sacc : 0.0, lane, sub, sup, mrow);
+            double z = bj_trim_group<8>(own ? sacc : 0.0, lane, sub, sup, mrow);
+            if constexpr (ND) z = pc + z;   // w = p + M^-1 (C p)
             if (own) {
                 st_wt(a.w_out + row, z);
                 wbuf[tid - BAND_OFF] = z;
@@ -532,7 +569,7 @@ __global__ __launch_bounds__(BAND_T) __attribute__((amdgpu_waves_per_eu(band_wpe
 // +2 / +5 us, j = 6-12 +6 ... +20 us each (the operands' registers held across the SpMV + dots);
 // the same signs on C2 and the C3 slabs
 template <int J> constexpr bool band_spf_j() { return J == 0 || J == 3 || J == 4; }
-template <int J> static void launch_band_one_rank(const BandK &a0, int grid, hipStream_t s) {
+template <int J, int ND> static void launch_band_one_rank(const BandK &a0, int grid, hipStream_t s) {
     BandK a = a0;
     if constexpr (!band_spf_j<J>()) a.opt &= ~1;
     const dim3 g(grid), blk(BAND_T);
@@ -540,14 +577,14 @@ template <int J> static void launch_band_one_rank(const BandK &a0, int grid, hip
     // 745-925 -> 709-875 us, j18 991 -> 970; with the register prefetch (J <= 12, two lines ahead)
     // it cost 11-35 us per launch
     if constexpr (J > BAND_PF) {
-        if (a.opt & 8) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 9>), g, blk, 0, s, a); return; }
+        if (a.opt & 8) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 9 | ND>), g, blk, 0, s, a); return; }
     }
     if constexpr (J <= BAND_J3) {
-        if ((a.opt & 3) == 3) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 3>), g, blk, 0, s, a); return; }
-        if ((a.opt & 3) == 2) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 2>), g, blk, 0, s, a); return; }
+        if ((a.opt & 3) == 3) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 3 | ND>), g, blk, 0, s, a); return; }
+        if ((a.opt & 3) == 2) { hipLaunchKernelGGL((k_band_step<5, J, 2, false, 2 | ND>), g, blk, 0, s, a); return; }
     }
-    if (a.opt & 1) hipLaunchKernelGGL((k_band_step<5, J, 2, false, 1>), g, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_band_step<5, J, 2, false>), g, blk, 0, s, a);
+    if (a.opt & 1) hipLaunchKernelGGL((k_band_step<5, J, 2, false, 1 | ND>), g, blk, 0, s, a);
+    else hipLaunchKernelGGL((k_band_step<5, J, 2, false, ND>), g, blk, 0, s, a);
 }
 
 // across ranks (ghost lines, canonical rows, line-separable values): the same variants as one rank
@@ -555,21 +592,21 @@ template <int J> static void launch_band_one_rank(const BandK &a0, int grid, hip
 // third workgroup per CU at low j, no LDS-DMA prefetch at high j), which the one-rank slab
 // projections (--comm-solo: no ghost lines) did not see.  The ghost lines' update operands come from
 // the ghost buffer in load(); the DMA prefetch skips them (l2_prefetch's ghostl)
-template <int J> static void launch_band_ghost(const BandK &a0, int grid, hipStream_t s) {
+template <int J, int ND> static void launch_band_ghost(const BandK &a0, int grid, hipStream_t s) {
     BandK a = a0;
     if constexpr (!band_spf_j<J>()) a.opt &= ~1;
     const dim3 g(grid), blk(BAND_T);
     if constexpr (J > BAND_PF) {
-        if (a.opt & 8) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 9>), g, blk, 0, s, a); return; }
+        if (a.opt & 8) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 9 | ND>), g, blk, 0, s, a); return; }
     }
     if constexpr (J <= BAND_J3) {
-        if ((a.opt & 3) == 3) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 3>), g, blk, 0, s, a); return; }
-        if ((a.opt & 3) == 2) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 2>), g, blk, 0, s, a); return; }
+        if ((a.opt & 3) == 3) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 3 | ND>), g, blk, 0, s, a); return; }
+        if ((a.opt & 3) == 2) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 2 | ND>), g, blk, 0, s, a); return; }
     }
     if constexpr (J > BAND_J3 && J <= BAND_PF) {
-        if (a.opt & 1) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 1>), g, blk, 0, s, a); return; }
+        if (a.opt & 1) { hipLaunchKernelGGL((k_band_step<5, J, 2, true, 1 | ND>), g, blk, 0, s, a); return; }
     }
-    hipLaunchKernelGGL((k_band_step<5, J, 2>), g, blk, 0, s, a);
+    hipLaunchKernelGGL((k_band_step<5, J, 2, true, ND>), g, blk, 0, s, a);
 }
 
 hipError_t launch_band_step(const BandK &a, int grid, int wu, hipStream_t s) {
@@ -580,8 +617,13 @@ hipError_t launch_band_step(const BandK &a, int grid, int wu, hipStream_t s) {
     switch (a.j) {
 #define VTK_BAND_J(J_)                                                                                           \
     case J_:                                                                                                     \
-        if (a.lsv && a.canon && !a.ghost) launch_band_one_rank<J_>(a, grid, s); \
-        else if (a.lsv && a.canon) launch_band_ghost<J_>(a, grid, s); \
+        if (a.lsv && a.canon && !a.ghost) { \
+            if (a.opt & 64) launch_band_one_rank<J_, 64>(a, grid, s); \
+            else launch_band_one_rank<J_, 0>(a, grid, s); \
+        } else if (a.lsv && a.canon) { \
+            if (a.opt & 64) launch_band_ghost<J_, 64>(a, grid, s); \
+            else launch_band_ghost<J_, 0>(a, grid, s); \
+        } \
         else if (a.lsv) hipLaunchKernelGGL((k_band_step<5, J_, 1>), dim3(grid), dim3(BAND_T), 0, s, a); \
         else hipLaunchKernelGGL((k_band_step<5, J_>), dim3(grid), dim3(BAND_T), 0, s, a); \
         break;
@@ -1270,6 +1312,9 @@ hipError_t launch_g4_ring(const Grid4 &g, const double *x, const double *halo, c
 // with M^-1 the tridiagonal BJ(8) of bj_trim_group (the same operations as k_sell's TRIM
 // epilogue).  The reductions: per lane over its rows in line order, then wave_sum, then the
 // waves in order -- one partial per workgroup (PREC_DC: launch_dc_dots' layout).
+//   EPI_PREC_DC_ND  EPI_PREC_DC as z = x + M^-1 (C x), no read of D (the band step's OPT bit 6):
+//                   step 0 of a band cycle forms its w by the same operator expression as the
+//                   band steps after it.  The residual epilogues keep D: they need r = b - A x
 // halo (distributed, vtk_csr::band_ghost): the two neighbour lines (blocks lblk = left and
 // 1 - lblk = right of L doubles, after halo_exchange), xord their place in the stored order
 struct LsvEpiK {
@@ -1281,8 +1326,10 @@ struct LsvEpiK {
     const double *halo;
     int lblk, xord;
 };
-template <int EPI>
+template <int EPI_>
 __global__ __launch_bounds__(BAND_T) void k_lsv_ring_epi(LsvEpiK a) {
+    constexpr bool ND = EPI_ == EPI_PREC_DC_ND;
+    constexpr int EPI = ND ? (int)EPI_PREC_DC : EPI_;
     __shared__ double ring[4 * BAND_T];
     __shared__ double red[3][BAND_T / 64];
     if (stopped(a.stop_col, a.col)) return;
@@ -1317,7 +1364,7 @@ __global__ __launch_bounds__(BAND_T) void k_lsv_ring_epi(LsvEpiK a) {
             nxv = inl ? __builtin_nontemporal_load(line_ptr(it + 1) + v) : 0.0;
             if (own && it + 1 >= 2) {
                 const int64_t rr = (int64_t)(xa + it - 1) * L + v;
-                nd = __builtin_nontemporal_load(lsv + rr);
+                if constexpr (!ND) nd = __builtin_nontemporal_load(lsv + rr);
                 if constexpr (BJ) nm = __builtin_nontemporal_load(a.mtri + rr);
                 if constexpr (HB) nb = __builtin_nontemporal_load(a.b + rr);
             }
@@ -1339,7 +1386,26 @@ __global__ __launch_bounds__(BAND_T) void k_lsv_ring_epi(LsvEpiK a) {
             const double t3 = tv1 * ring[sx + tid + (tid < BAND_T - 1 ? 1 : 0)];
             const bool h1 = v > 0, h3 = v < L - 1;
             double sa = 0.0;
-            if (ord == P_MID) {
+            if constexpr (ND) {
+                // y = C x: the v -+ 1 terms only across a block edge, no diagonal term
+                const bool c1 = h1 && ii == 0, c3 = h3 && ii == 7;
+                if (ord == P_MID) {
+                    sa = sa + t0;
+                    sa = c1 ? sa + t1 : sa;
+                    sa = c3 ? sa + t3 : sa;
+                    sa = sa + t4;
+                } else if (ord == P_FIRST) {
+                    sa = c1 ? sa + t1 : sa;
+                    sa = c3 ? sa + t3 : sa;
+                    sa = sa + t4;
+                    sa = sa + t0;
+                } else {
+                    sa = sa + t4;
+                    sa = sa + t0;
+                    sa = c1 ? sa + t1 : sa;
+                    sa = c3 ? sa + t3 : sa;
+                }
+            } else if (ord == P_MID) {
                 sa = sa + t0;
                 sa = h1 ? sa + t1 : sa;
                 sa = sa + t2;
@@ -1367,7 +1433,8 @@ __global__ __launch_bounds__(BAND_T) void k_lsv_ring_epi(LsvEpiK a) {
             if constexpr (BJ) {
                 const double sub = (own && h1 && ii > 0) ? 0.0 + tv0 : 0.0;
                 const double sup = (own && h3 && ii < 7) ? 0.0 + tv1 : 0.0;
-                const double z = bj_trim_group<8>(own ? out : 0.0, lane, sub, sup, own ? mrow : 1.0);
+                double z = bj_trim_group<8>(own ? out : 0.0, lane, sub, sup, own ? mrow : 1.0);
+                if constexpr (ND) z = xr + z;   // x + M^-1 (C x)
                 if constexpr (EPI == EPI_RESID_PREC) {
                     if (own) acc1 += z * z;
                 } else {
@@ -1409,9 +1476,10 @@ hipError_t launch_lsv_ring_epi(int epi, const double *lsv, const double *x, cons
     if (n <= 0 || n > INT32_MAX / 2 || L <= 0 || n % L != 0 || H < 1 || X < (halo ? 2 : 3) || ring_wgs < 1 ||
         (halo && (lblk < 0 || lblk > 1)))
         return hipErrorInvalidValue;
-    const bool bj = epi == EPI_RESID_PREC || epi == EPI_PREC_DC;
+    const bool dc = epi == EPI_PREC_DC || epi == EPI_PREC_DC_ND;
+    const bool bj = epi == EPI_RESID_PREC || dc;
     if ((bj && !mtri) || ((epi == EPI_RESID || epi == EPI_RESID_PREC) && (!b || !p0)) ||
-        (epi == EPI_RESID_PREC && !p1) || (epi == EPI_PREC_DC && !dcpart) || L % 8 != 0)
+        (epi == EPI_RESID_PREC && !p1) || (dc && !dcpart) || L % 8 != 0)
         return hipErrorInvalidValue;
     // one partial per workgroup: at most GMAX
     const int64_t R = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ring_wgs / H, X / 2), GMAX / H));
@@ -1422,6 +1490,7 @@ hipError_t launch_lsv_ring_epi(int epi, const double *lsv, const double *x, cons
         case EPI_RESID: hipLaunchKernelGGL(k_lsv_ring_epi<EPI_RESID>, g, blk, 0, s, a); break;
         case EPI_RESID_PREC: hipLaunchKernelGGL(k_lsv_ring_epi<EPI_RESID_PREC>, g, blk, 0, s, a); break;
         case EPI_PREC_DC: hipLaunchKernelGGL(k_lsv_ring_epi<EPI_PREC_DC>, g, blk, 0, s, a); break;
+        case EPI_PREC_DC_ND: hipLaunchKernelGGL(k_lsv_ring_epi<EPI_PREC_DC_ND>, g, blk, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

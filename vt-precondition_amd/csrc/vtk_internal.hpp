@@ -200,7 +200,7 @@ struct Tuning {
     int band_lsv = 1;         // solver launches read the line-separable values (else SELL values)
     int sell_canon = 1;       // ... and canonical rows' columns from the line index (no codes)
     int band_canon = 1;       // the band step reads no codes on canonical rows
-    int band_opt = 63;        // band step variant bits (vtk_band.hip k_band_step OPT; in-process A/B
+    int band_opt = 127;       // band step variant bits (vtk_band.hip k_band_step OPT; in-process A/B
                               // C3: SpMV operands prefetched j00 254 -> 217 us, + three workgroups per
                               // CU for j <= BAND_J3: j00 190, j01 283 -> 246 us; solve 42.66 -> 42.31 ms;
                               // round 6: bit 2, a line range's two parts on one XCD: 40.56 -> 40.30 ms;
@@ -212,7 +212,10 @@ struct Tuning {
                               // (DESIGN.md §3i): C3 37.37 -> 36.62 ms (two runs: -2.0 %, -1.7 %), at
                               // every size: C2 10.28 -> 10.21, C3/2 slab 18.95 -> 18.86, C3/8 slab
                               // 6.23 -> 6.16 ms (profiles/serpentine_ab*.json); every step reversed
-                              // instead of every other one: 38.79 vs 38.78 ms, nothing)
+                              // instead of every other one: 38.79 vs 38.78 ms, nothing);
+                              // bit 6 (64), no read of the diagonal table: w = p + M^-1 (A - M) p with
+                              // M the tridiagonal BJ(8) of A's current values (the band
+                              // step and step 0 of its cycle; 8 B per row fewer per launch)
     int band_long_rows = 16000000;   // band_opt bits 3 and 4 only on basis vectors of >= this many rows
                               // (in-process A/B, round 6: bit 3 on vs off, C3 20M rows 39.30 vs 39.78 ms,
                               // C3/2 slab 10M 20.20 vs 20.09, C2 5M 10.98 vs 10.86, C3/8 slab 2.5M 6.53
@@ -406,7 +409,8 @@ hipError_t launch_index_range(const int32_t *idx, int64_t n, int *mm, hipStream_
 inline int spmv_grid(const SpmvIn &in) { return (in.sell && in.groups) ? in.groups->grid : in.tiles->grid; }
 
 // EPI_PREC_DC: w = M^-1 A p_j plus the DCGS2 step's dot products (launch_spmv_dc)
-enum Epi { EPI_PLAIN = 0, EPI_RESID = 1, EPI_PREC = 2, EPI_RESID_PREC = 3, EPI_PREC_DC = 4 };
+// EPI_PREC_DC_ND (launch_lsv_ring_epi only): EPI_PREC_DC as w = p_j + M^-1 (A - M) p_j, D not read
+enum Epi { EPI_PLAIN = 0, EPI_RESID = 1, EPI_PREC = 2, EPI_RESID_PREC = 3, EPI_PREC_DC = 4, EPI_PREC_DC_ND = 5 };
 
 // y = A x (PLAIN); y = b - A x, part0 = sum y^2 (RESID); y = M^-1 A x with M = BJ(inv, bs)
 // or identity (inv == null), part0 = sum y^2, part1 = sum v0*y (PREC, v0 may be null);
@@ -584,7 +588,8 @@ hipError_t launch_lsv_build(const int32_t *indptr, const int32_t *indices, const
 // k_sell's plain SpMV, the same bits.  halo != null: the distributed layout (lblk the left block)
 // the x-line ring SpMV with the solver's epilogues (one rank, canonical rows; k_lsv_ring_epi):
 // EPI_RESID (y = b - A x, p0 = |r|^2 partials), EPI_RESID_PREC (y = M^-1 (b - A x), p0, p1 =
-// |r|^2, |z|^2), EPI_PREC_DC (y = M^-1 A x, DCGS2 step-0 dots |x|^2, x.y, |y|^2 into dcpart);
+// |r|^2, |z|^2), EPI_PREC_DC (y = M^-1 A x, DCGS2 step-0 dots |x|^2, x.y, |y|^2 into dcpart;
+// EPI_PREC_DC_ND: the same without the read of D);
 // *grid_out partials (<= GMAX)
 hipError_t launch_lsv_ring_epi(int epi, const double *lsv, const double *x, const double *b, const double *mtri,
                                double *y, double *p0, double *p1, double *dcpart, int64_t n, int L, int ring_wgs,
