@@ -374,6 +374,59 @@ int vtk_gmres_set_orth(vtk_ctx *ctx, int orth);
  * (vtk_csr_set_line_band); off keeps the separate update pass and fused SpMV step */
 int vtk_gmres_set_band(vtk_ctx *ctx, int on);
 
+/* ---- capture of one restart cycle (a TEST HOOK: off by default, not part of the integration
+ * surface; additive, ABI 6) -----------------------------------------------------------------
+ * The solver's workspace after a solve does not show a cycle's Arnoldi factorisation: the
+ * cycle-end residual writes the next v0 direction into V[0], and a later cycle overwrites
+ * everything.  An armed capture copies, device to device on the context's stream, x at the
+ * start of the chosen cycle (before the cycle's x update, wherever that runs) and, between the
+ * x update and the cycle-end residual, all restart + 1 columns of V, H (rotated), S, giv and,
+ * under DCGS2, Hraw (the unrotated Hessenberg columns) and the step coefficients.
+ *   cycle >= 0: that 0-based restart cycle of every following vtk_gmres on the context;
+ *   cycle == -1 (default): off -- the solve issues no allocation, copy or synchronisation for it;
+ *   cycle == -2: every cycle, the last one run is kept.
+ * The buffer belongs to the context and is freed with it.  Across ranks each rank captures its
+ * own rows; no collective is added.
+ *
+ * vtk_arnoldi_info.final_cols: the leading columns of V that are FINAL at cycle end, i.e. hold
+ * v_0 .. v_{final_cols-1} normalised (and, under DCGS2, re-orthogonalised).  The rule:
+ *   MGS: the tail of column c stores v_{c+1}: final_cols = cols + 1 (cols on a breakdown, whose
+ *        last vector is stored unnormalised);
+ *   DCGS2 (split, fused, ring, line and band steps alike): v_j (j >= 1) is stored by the update
+ *        pass of step j, one step after its candidate p_j.  The step whose scalar kernel stops
+ *        the cycle (xup_tag = j; the last column of a full cycle stops it at j = restart - 1 when
+ *        it commits early) turns its update pass into the x update: V[j] keeps the candidate p_j
+ *        -- or, on the band path, which never stores p_j for j <= restart - 2, whatever an earlier
+ *        cycle left there -- and v_j enters x recomputed, not as a column of V.
+ *        final_cols = max(xup_tag, 1); a cycle closed by the closing reduction (xup_tag < 0)
+ *        ran every update pass: final_cols = restart.
+ * The Arnoldi relation B v_c = V[:, :c+2] h_c can be checked for c + 1 < final_cols; every such
+ * column was finalised exactly (an early commit always stops the cycle at its column).
+ * H is column-major with leading dimension restart + 1 (column c at c (restart + 1)), Hraw
+ * likewise with restart + 1 columns; h_{c+1,c} of a column committed early is the tentative nu
+ * (VTK_CAP_NU), its Hraw rows 0..c the tentative column. */
+typedef struct {
+    int64_t n_local, ld;   /* rows of this rank; leading dimension of V                    */
+    int restart, cycle;    /* m; the cycle captured                                         */
+    int cols, final_cols;  /* columns committed to H; final leading columns of V           */
+    int orth, band;        /* VTK_ORTH_MGS / VTK_ORTH_DCGS2; 1: the line-band step ran      */
+    int has_hraw;          /* 1 under DCGS2                                                 */
+    int stop_col, breakdown, xup_tag;   /* the cycle's device record (stop_col >= 2^30: ran out) */
+} vtk_arnoldi_info;
+enum { VTK_CAP_V = 0,          /* (restart + 1) * ld doubles                                */
+       VTK_CAP_X_IN = 1,       /* n_local doubles                                           */
+       VTK_CAP_H = 2,          /* restart * (restart + 1) doubles                           */
+       VTK_CAP_S = 3,          /* restart + 1                                               */
+       VTK_CAP_GIV = 4,        /* 2 restart: c_0 s_0 c_1 s_1 ...                            */
+       VTK_CAP_HRAW = 5,       /* (restart + 1)^2 doubles (DCGS2)                           */
+       VTK_CAP_COMMITTED = 6,  /* restart + 1 int32 (DCGS2)                                 */
+       VTK_CAP_NU = 7 };       /* 1 double: the last tentative h_{j+1,j} (DCGS2)            */
+int vtk_gmres_capture(vtk_ctx *ctx, int cycle);
+/* VTK_ERR_STATE when nothing is captured: never armed, the chosen cycle not reached, or a later
+ * vtk_gmres on the context ran without capture */
+int vtk_gmres_captured(vtk_ctx *ctx, vtk_arnoldi_info *info);
+int vtk_gmres_captured_read(vtk_ctx *ctx, int what, void *dst, int ptr_kind);
+
 /* scipy.sparse.linalg.bicgstab semantics (iterative.py, bicgstab, callback=None): right-
  * preconditioned BiCGStab, M approximating A^-1 (NULL: none); x holds x0 on entry.  info as
  * SciPy's: 0 converged (||r|| or ||s|| of the recurrence below max(atol, rtol ||b||)), -10 the

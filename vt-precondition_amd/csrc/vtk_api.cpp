@@ -1815,6 +1815,27 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
     }
     HIPCHK(c, hipMemsetAsync(s.H, 0, (size_t)m * (m + 1) * sizeof(double), c->stream));
     HIPCHK(c, hipMemsetAsync(s.giv, 0, (size_t)2 * m * sizeof(double), c->stream));
+    // capture of one restart cycle (vtk_gmres_capture, a test hook): the buffer once per solve; a
+    // solve that runs unarmed drops what an earlier one captured
+    const bool cap_on = c->cap_cycle != -1;
+    c->cap_valid = false;
+    const size_t cap_hsg = (size_t)m * (m + 1) + (m + 1) + 2 * m, cap_hraw = (size_t)(m + 1) * (m + 1);
+    double *cap_x = nullptr, *cap_V = nullptr, *cap_H = nullptr, *cap_Hraw = nullptr, *cap_cf = nullptr;
+    if (cap_on) {
+        const size_t need = ((size_t)(m + 2) * s.ld + cap_hsg + cap_hraw + sizeof(DcCoef) / 8 + 8) * sizeof(double);
+        if (c->cap_bytes < need) {
+            if (c->cap) (void)hipFree(c->cap);
+            c->cap = nullptr;
+            c->cap_bytes = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->cap), need));
+            c->cap_bytes = need;
+        }
+        cap_x = c->cap;
+        cap_V = cap_x + s.ld;
+        cap_H = cap_V + (size_t)(m + 1) * s.ld;
+        cap_Hraw = cap_H + cap_hsg;
+        cap_cf = cap_Hraw + cap_hraw;
+    }
     GmresState *ds = c->d_state, *hs = c->h_state;
     std::memset(hs, 0, sizeof(GmresState));
     hs->stop_col = BIG_COL;
@@ -1968,6 +1989,9 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
         const int *stop = &ds->stop_col;
         *mirror = BIG_COL;
         int enq = 0;
+        // x as the cycle finds it: the x update may run inside an update pass of the cycle
+        const bool cap_now = cap_on && (c->cap_cycle == -2 || c->cap_cycle == it);
+        if (cap_now) HIPCHK(c, hipMemcpyAsync(cap_x, x, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         if (dc) {
             HIPCHK(c, hipMemsetAsync(s.cf->committed, 0, sizeof(s.cf->committed), c->stream));
             TRY(dcgs2_cycle(s, stop, mirror, ev));
@@ -2003,6 +2027,14 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
         const size_t xup_idx = c->prof_pending.size();
         { Prof pf(c, "xupdate", -1, 0.0);   // bytes set once the stop column is known
           SOFT(launch_xupdate(s.H, s.S, s.V, s.ld, x, n, m, ds, s.G, c->stream)); }
+        if (cap_now) {   // before residual() writes the next v0 direction into V[0]
+            HIPCHK(c, hipMemcpyAsync(cap_V, s.V, (size_t)(m + 1) * s.ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(cap_H, s.H, cap_hsg * sizeof(double), hipMemcpyDeviceToDevice, c->stream));   // H | S | giv
+            if (dc) {
+                HIPCHK(c, hipMemcpyAsync(cap_Hraw, s.Hraw, cap_hraw * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(cap_cf, s.cf, sizeof(DcCoef), hipMemcpyDeviceToDevice, c->stream));
+            }
+        }
         TRY(residual());
         // across ranks: the cycle's failure vote (a launch of some rank failed in this cycle; the
         // per-step vote has already stopped the Arnoldi steps at the same step on every rank)
@@ -2021,6 +2053,14 @@ int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, 
                                              "; every rank left the solve there");
         }
         const int last = hs->stop_col < m ? hs->stop_col : m - 1;
+        if (cap_now) {
+            // the columns of V that are final at cycle end (the rule: include/vtkrylov.h)
+            const int fin = dc ? (hs->xup_tag >= 0 ? std::max(hs->xup_tag, 1) : m)
+                               : last + 1 + (hs->breakdown ? 0 : 1);
+            c->cap_info = vtk_arnoldi_info{n, s.ld, m, (int)it, last + 1, fin, dc ? VTK_ORTH_DCGS2 : VTK_ORTH_MGS,
+                                           s.band ? 1 : 0, dc ? 1 : 0, hs->stop_col, hs->breakdown, hs->xup_tag};
+            c->cap_valid = true;
+        }
         if (c->prof_on) {
             const double xb = n8 * (last + 1) + 2 * n8;   // V[0..last] (or V_last and p_last), x in/out
             if (xup_idx < c->prof_pending.size()) c->prof_pending[xup_idx].bytes = xb;
@@ -2406,6 +2446,7 @@ void vtk_ctx_destroy(vtk_ctx *c) {
     (void)hipFree(c->d_scal);
     (void)hipFree(c->d_state);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->cap) (void)hipFree(c->cap);
     if (c->h_state) (void)hipHostFree(c->h_state);
     if (c->h_stop) (void)hipHostFree(c->h_stop);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
@@ -3088,6 +3129,48 @@ int vtk_gmres_set_orth(vtk_ctx *c, int orth) {
     if (!c || (orth != VTK_ORTH_MGS && orth != VTK_ORTH_DCGS2 && orth != VTK_ORTH_AUTO))
         return fail(c, VTK_ERR_ARG, "vtk_gmres_set_orth: unknown scheme");
     c->orth = orth;
+    return VTK_OK;
+}
+
+int vtk_gmres_capture(vtk_ctx *c, int cycle) {
+    if (!c || cycle < -2) return fail(c, VTK_ERR_ARG, "vtk_gmres_capture: cycle must be >= 0, -1 (off) or -2 (every cycle)");
+    c->cap_cycle = cycle;
+    return VTK_OK;
+}
+
+int vtk_gmres_captured(vtk_ctx *c, vtk_arnoldi_info *info) {
+    if (!c || !info) return VTK_ERR_ARG;
+    if (!c->cap_valid) return fail(c, VTK_ERR_STATE, "vtk_gmres_captured: no restart cycle has been captured");
+    *info = c->cap_info;
+    return VTK_OK;
+}
+
+int vtk_gmres_captured_read(vtk_ctx *c, int what, void *dst, int kind) {
+    if (!c || !dst || (kind != VTK_PTR_HOST && kind != VTK_PTR_DEVICE)) return fail(c, VTK_ERR_ARG, "vtk_gmres_captured_read: bad argument");
+    if (!c->cap_valid) return fail(c, VTK_ERR_STATE, "vtk_gmres_captured_read: no restart cycle has been captured");
+    const vtk_arnoldi_info &ci = c->cap_info;
+    const size_t m = (size_t)ci.restart, ld = (size_t)ci.ld;
+    const double *V = c->cap + ld, *H = V + (m + 1) * ld, *S = H + m * (m + 1), *giv = S + (m + 1);
+    const double *Hraw = giv + 2 * m;
+    const DcCoef *cf = reinterpret_cast<const DcCoef *>(Hraw + (m + 1) * (m + 1));
+    const void *src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+    case VTK_CAP_V: src = V; bytes = (m + 1) * ld * sizeof(double); break;
+    case VTK_CAP_X_IN: src = c->cap; bytes = (size_t)ci.n_local * sizeof(double); break;
+    case VTK_CAP_H: src = H; bytes = m * (m + 1) * sizeof(double); break;
+    case VTK_CAP_S: src = S; bytes = (m + 1) * sizeof(double); break;
+    case VTK_CAP_GIV: src = giv; bytes = 2 * m * sizeof(double); break;
+    case VTK_CAP_HRAW: src = Hraw; bytes = (m + 1) * (m + 1) * sizeof(double); break;
+    case VTK_CAP_COMMITTED: src = cf->committed; bytes = (m + 1) * sizeof(int); break;
+    case VTK_CAP_NU: src = &cf->nu; bytes = sizeof(double); break;
+    default: return fail(c, VTK_ERR_ARG, "vtk_gmres_captured_read: unknown item");
+    }
+    if (what >= VTK_CAP_HRAW && !ci.has_hraw) return fail(c, VTK_ERR_STATE, "vtk_gmres_captured_read: the captured cycle ran MGS (no Hraw)");
+    if (bytes == 0) return VTK_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, kind == VTK_PTR_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return VTK_OK;
 }
 

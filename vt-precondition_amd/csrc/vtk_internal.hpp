@@ -270,6 +270,13 @@ struct vtk_ctx {
     int *d_stop = nullptr;                // device alias of h_stop
     void *ws = nullptr;                   // solver workspace (grow-only, reused across solves)
     size_t ws_bytes = 0;
+    // capture of one restart cycle (vtk_gmres_capture; a test hook, off by default)
+    // cap: x_in[ld] | V[(m+1) ld] | H, S, giv | Hraw[(m+1)^2] | DcCoef
+    int cap_cycle = -1;
+    double *cap = nullptr;
+    size_t cap_bytes = 0;
+    bool cap_valid = false;
+    vtk_arnoldi_info cap_info{};
     // kernel profile (vtk_profile_enable)
     struct ProfPending { int cls; int col; double bytes; hipEvent_t e0, e1; };
     struct ProfAcc { std::string name; int64_t launches = 0; double seconds = 0, bytes = 0; };

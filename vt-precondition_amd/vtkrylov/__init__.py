@@ -30,7 +30,8 @@ from ._abi import check, lib
 __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "vlasov_operator", "block_jacobi",
            "gmres", "VlasovParams", "vlasov_params", "rhs_splitmix", "partition_rows",
            "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi",
-           "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats"]
+           "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats",
+           "ArnoldiCapture", "last_arnoldi"]
 
 VlasovParams = _abi.VlasovParams
 
@@ -176,6 +177,21 @@ class Context:
             finally:
                 for k, v in old.items():
                     self.set_tuning(k, v)
+        return cm()
+
+    def capture_arnoldi(self, cycle: int = 0):
+        """``with ctx.capture_arnoldi(0): vk.gmres(...)`` -- a test hook: the solves of the block
+        copy restart cycle ``cycle`` (0-based; -2: the last cycle run) aside for
+        :func:`last_arnoldi` (``vtk_gmres_capture``).  Disarmed on exit."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            check(lib().vtk_gmres_capture(self._h, int(cycle)), self._h)
+            try:
+                yield self
+            finally:
+                check(lib().vtk_gmres_capture(self._h, -1), self._h)
         return cm()
 
     band = True
@@ -754,6 +770,57 @@ _last_stats: SolveStats | None = None
 
 def last_stats() -> SolveStats | None:
     return _last_stats
+
+
+@dataclass
+class ArnoldiCapture:
+    """One captured restart cycle (``vtk_gmres_captured``; include/vtkrylov.h states which columns
+    of ``V`` are final).  ``V``: (restart + 1, n_local), row k = column k of the basis.  ``H``:
+    (restart, restart + 1), row c = the rotated column c; ``Hraw`` (DCGS2): (restart + 1,
+    restart + 1), row c = the unrotated column c.  ``giv``: (restart, 2) pairs (c, s)."""
+    n_local: int
+    restart: int
+    cycle: int
+    cols: int
+    final_cols: int
+    orth: int
+    band: int
+    stop_col: int
+    breakdown: int
+    xup_tag: int
+    V: np.ndarray
+    x_in: np.ndarray
+    H: np.ndarray
+    S: np.ndarray
+    giv: np.ndarray
+    Hraw: np.ndarray | None = None
+    committed: np.ndarray | None = None
+    nu: float | None = None
+
+
+def last_arnoldi(ctx: Context | None = None) -> ArnoldiCapture:
+    """The restart cycle captured by the last solve under ``ctx.capture_arnoldi`` (VtkError with
+    status ERR_STATE when there is none)."""
+    ctx = ctx or default_context()
+    ai = _abi.ArnoldiInfo()
+    check(lib().vtk_gmres_captured(ctx.handle, C.byref(ai)), ctx.handle)
+    m, ld, n = ai.restart, ai.ld, ai.n_local
+
+    def rd(what, count, dtype=np.float64):
+        a = np.zeros(count, dtype=dtype)
+        check(lib().vtk_gmres_captured_read(ctx.handle, what, _np_ptr(a), _abi.PTR_HOST), ctx.handle)
+        return a
+    out = ArnoldiCapture(
+        n_local=n, restart=m, cycle=ai.cycle, cols=ai.cols, final_cols=ai.final_cols, orth=ai.orth, band=ai.band,
+        stop_col=ai.stop_col, breakdown=ai.breakdown, xup_tag=ai.xup_tag,
+        V=rd(_abi.CAP_V, (m + 1) * ld).reshape(m + 1, ld)[:, :n].copy(), x_in=rd(_abi.CAP_X_IN, n),
+        H=rd(_abi.CAP_H, m * (m + 1)).reshape(m, m + 1), S=rd(_abi.CAP_S, m + 1),
+        giv=rd(_abi.CAP_GIV, 2 * m).reshape(m, 2))
+    if ai.has_hraw:
+        out.Hraw = rd(_abi.CAP_HRAW, (m + 1) * (m + 1)).reshape(m + 1, m + 1)
+        out.committed = rd(_abi.CAP_COMMITTED, m + 1, np.int32)
+        out.nu = float(rd(_abi.CAP_NU, 1)[0])
+    return out
 
 
 def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=None,

@@ -124,6 +124,9 @@ PROTOTYPES = {
                                C.POINTER(C.c_int), C.POINTER(BicgstabStats)]),
     "vtk_gmres_set_orth": (C.c_int, [P, C.c_int]),
     "vtk_gmres_set_band": (C.c_int, [P, C.c_int]),
+    "vtk_gmres_capture": (C.c_int, [P, C.c_int]),
+    "vtk_gmres_captured": (C.c_int, [P, C.c_void_p]),
+    "vtk_gmres_captured_read": (C.c_int, [P, C.c_int, P, C.c_int]),
     "vtk_bjacobi_create_ex": (C.c_int, [P, C.c_int, C.c_int, C.c_void_p]),
     "vtk_profile_enable": (C.c_int, [P, C.c_int]),
     "vtk_profile_read": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_int)]),
@@ -131,6 +134,16 @@ PROTOTYPES = {
 
 
 ABI_VERSION = 6   # include/vtkrylov.h VTK_ABI_VERSION
+
+
+class ArnoldiInfo(C.Structure):
+    _fields_ = [("n_local", C.c_int64), ("ld", C.c_int64), ("restart", C.c_int), ("cycle", C.c_int),
+                ("cols", C.c_int), ("final_cols", C.c_int), ("orth", C.c_int), ("band", C.c_int),
+                ("has_hraw", C.c_int), ("stop_col", C.c_int), ("breakdown", C.c_int), ("xup_tag", C.c_int)]
+
+
+# vtk_gmres_captured_read items
+CAP_V, CAP_X_IN, CAP_H, CAP_S, CAP_GIV, CAP_HRAW, CAP_COMMITTED, CAP_NU = range(8)
 
 
 class BandGeometry(C.Structure):
