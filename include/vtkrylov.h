@@ -13,7 +13,9 @@
  *   vtk_bjacobi_apply   <- LinearOperator(matvec=einsum('bij,bj->bi'))
  *   vtk_linejacobi_*    <- LinearOperator(matvec=splu(M).solve), M = diagonal + x-line
  *                          couplings (line-implicit x-direction solve)
- *   vtk_gmres           <- scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=, restart=,
+ *   vtk_lineproduct_*   <- LinearOperator(matvec=lambda r: lu2.solve(D * lu1.solve(r))),
+ *                          lu_i = splu(M_i): two line directions
+ *   vtk_gmres          <- scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=, restart=,
  *                          maxiter=, M=) (scipy/sparse/linalg/_isolve/iterative.py:582-841)
  * The config/entry layer the reference does have (XML node lookups, ini_info.py:72-118;
  * step objects with main(), hypervisor.py:589-594) is mirrored in Python by
@@ -174,7 +176,7 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * nowhere else (fail_step is a test hook: this rank fails its DCGS2 step of that index in the
  * first cycle, vtk_gmres).  Keys: band, band_lsv, sell_canon, band_canon, band_opt, band_long_rows, lsv_ring,
  * prof_perj, comm_solo, auto_band, grid4, c4_fused, g4_ring, g4_gr, g4_fast, line_fuse, cyc_ring,
- * bcg_fuse, fail_step.
+ * line2_dc, bcg_fuse, fail_step.
  * VTK_ERR_ARG for an unknown key; a VTK_<KEY> variable of a key removed in round 5 draws a
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
  * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
@@ -322,7 +324,7 @@ void vtk_prec_destroy(vtk_prec *M);
  * (4D); seg dividing Nx / world makes M independent of the rank count.  VTK_ERR_SINGULAR
  * when a pivot is zero or not finite.  Apply with vtk_prec_apply (or vtk_bjacobi_apply); use
  * as vtk_gmres's M. */
-typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1 } vtk_prec_kind;
+typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1, VTK_PREC_LINE2 = 2 } vtk_prec_kind;
 int vtk_linejacobi_create(vtk_csr *A, int64_t stride, int64_t seg, vtk_prec **out);
 /* export the factors l | m | g (3 * n_local doubles; the oracle's orc_line_setup layout) */
 int vtk_linejacobi_factors(vtk_prec *M, double *f, int ptr_kind);
@@ -332,10 +334,29 @@ int vtk_linejacobi_factors(vtk_prec *M, double *f, int ptr_kind);
  * set_compact(0) forces the stored-factor apply; set_compact(1) fails when unavailable. */
 int vtk_linejacobi_set_compact(vtk_prec *M, int on);
 int vtk_linejacobi_get_compact(vtk_prec *M, int *in_use, int *available);
+/* ---- line product: two line directions ----------------------------------
+ * M = M1 D^-1 M2 = D + X + Y + X D^-1 Y, the approximate-factorisation (ADI-type) product of two
+ * line-Jacobi matrices of A: M_i is exactly vtk_linejacobi_create(A, stride_i, seg_i)'s matrix
+ * (the same kept couplings, cuts and Thomas factors), D[r] the sum of row r's stored diagonal
+ * entries, X and Y the off-diagonal parts of M1 and M2.  Apply: t = M1^-1 r, u = D .* t (one
+ * multiply per row), z = M2^-1 u -- bit-identical to the oracle's
+ * line_apply(lf2, D * line_apply(lf1, r)).  SciPy statement:
+ * LinearOperator(matvec=lambda r: lu2.solve(D * lu1.solve(r))) with lu_i = splu(M_i).
+ * 4D Vlasov operators: strides Ny*Nvx*Nvy (x) and Nvx*Nvy (y).  Both sweeps are rank-local.
+ * Argument checks per direction as vtk_linejacobi_create; VTK_ERR_SINGULAR when a pivot of
+ * either direction is zero or not finite (the smaller row is reported).  Apply, refresh and
+ * destroy through vtk_prec_apply / vtk_prec_refresh / vtk_prec_destroy; usable as vtk_gmres's
+ * and vtk_bicgstab's M and in vtk_precond_matvec.  The vtk_linejacobi_* calls refuse it
+ * (VTK_ERR_STATE).  Tuning key line2_dc (default 1): the DCGS2 step's dots fused behind the
+ * second sweep; 0: the plain second sweep, then the dots kernel.  (additive, ABI 6) */
+int vtk_lineproduct_create(vtk_csr *A, int64_t stride1, int64_t seg1, int64_t stride2, int64_t seg2,
+                           vtk_prec **out);
+/* which 0 / 1: the factors l | m | g of that direction (3 * n_local doubles); 2: D (n_local) */
+int vtk_lineproduct_factors(vtk_prec *M, int which, double *f, int ptr_kind);
 /* z = M^-1 r for any preconditioner; *kind = vtk_prec_kind */
 int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int ptr_kind);
 int vtk_prec_kind_of(vtk_prec *M, int *kind);
-/* Recompute M (BJ or line Jacobi) from its operator's current values into the storage
+/* Recompute M (BJ, line Jacobi or line product: both directions and D) from its operator's current values into the storage
  * it already owns.  *epoch (nullable) = the operator epoch M now corresponds to.
  * Block Jacobi: the setup M was created with (EXACT or MFMA), the tridiagonal check and the
  * remembered vtk_bjacobi_set_mode request again; VTK_ERR_ARG when an explicit TRIDIAG request

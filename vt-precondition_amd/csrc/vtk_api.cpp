@@ -86,6 +86,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {"prof_perj", &Tuning::prof_perj}, {"comm_solo", &Tuning::comm_solo}, {"auto_band", &Tuning::auto_band},
     {"grid4", &Tuning::grid4}, {"c4_fused", &Tuning::c4_fused}, {"g4_ring", &Tuning::g4_ring},
     {"g4_gr", &Tuning::g4_gr}, {"g4_fast", &Tuning::g4_fast}, {"line_fuse", &Tuning::line_fuse}, {"cyc_ring", &Tuning::cyc_ring},
+    {"line2_dc", &Tuning::line2_dc},
     {"bcg_fuse", &Tuning::bcg_fuse},
     {"fail_step", &Tuning::fail_step},
 };
@@ -177,8 +178,12 @@ void prof_flush(vtk_ctx *c, int last_col = 1 << 30) {
 BjOp bj_op(const vtk_prec *M) {
     BjOp o;
     if (!M) return o;
-    if (M->kind == VTK_PREC_LINE) {
+    if (M->kind == VTK_PREC_LINE || M->kind == VTK_PREC_LINE2) {
         o.line = &M->line;
+        if (M->kind == VTK_PREC_LINE2) {   // the product: both sweeps (launch_bj_apply)
+            o.line2 = &M->line2;
+            o.diag = M->d_diag;
+        }
         return o;
     }
     o.inv = M->d_inv;
@@ -196,12 +201,20 @@ BjOp bj_op(const vtk_prec *M) {
 }
 
 // profile class of a standalone preconditioner apply
-const char *prec_cls(const vtk_prec *M) { return M && M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply"; }
+const char *prec_cls(const vtk_prec *M) {
+    if (M && M->kind == VTK_PREC_LINE2) return "line2_apply";   // both sweeps of the product
+    return M && M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply";
+}
+
+// bytes per row of one direction's factors as a sweep reads them: m (compact) or l, m, g
+double line_row_bytes(const LineOp &L) { return L.compact ? 8.0 : 24.0; }
 
 // algorithmic bytes per row of one BJ application (tridiagonal: the SELL kernels read only m)
 double bj_row_bytes(const vtk_prec *M) {
     if (!M) return 0.0;
-    if (M->kind == VTK_PREC_LINE) return M->line.compact ? 8.0 : 24.0;   // m (compact) or l, m, g
+    if (M->kind == VTK_PREC_LINE) return line_row_bytes(M->line);
+    // the product: both directions' factors, D, and t = M1^-1 r written and read back
+    if (M->kind == VTK_PREC_LINE2) return line_row_bytes(M->line) + line_row_bytes(M->line2) + 8.0 + 16.0;
     if (bj_op(M).tri) return M->A->use_sell ? 8.0 : 24.0;
     return 8.0 * M->bs;
 }
@@ -1195,15 +1208,15 @@ int bj_factor(vtk_prec *M) {
     return VTK_OK;
 }
 
-// The same for line Jacobi (vtk_linejacobi_create / vtk_prec_refresh): Thomas factors into
-// M->line.f, then the x-invariance check of the couplings; the compact tables are built in a
-// scope-owned buffer and committed (or dropped) at the end.  A vtk_linejacobi_set_compact(0)
-// request is kept.  VTK_ERR_SINGULAR: a zero or non-finite pivot.
-int line_factor(vtk_prec *M) {
-    vtk_csr *A = M->A;
+// One line direction (line Jacobi, or either factor of the line product): Thomas factors into
+// L.f, then the x-invariance check of the couplings; the compact tables are built in a
+// scope-owned buffer and committed (or dropped) at the end.  compact_req / compact_ok: vtk_prec's
+// (a vtk_linejacobi_set_compact(0) request is kept).  A zero or non-finite pivot: bad_row = the
+// smallest such global row (else ~0), VTK_OK, and L.ac left as it was.
+int line_factor_op(vtk_csr *A, LineOp &L, int compact_req, bool &compact_ok, unsigned long long &bad_row) {
     vtk_ctx *c = A->ctx;
     DBuf bad, ext, acb;
-    const int64_t jn = M->line.jn;
+    const int64_t jn = L.jn;
     TRY(dalloc(c, bad, sizeof(unsigned long long)));
     TRY(dalloc(c, ext, 4 * std::max<int64_t>(jn, 1) * sizeof(unsigned long long)));
     TRY(dalloc(c, acb, 2 * (size_t)std::max<int64_t>(jn, 1) * sizeof(double)));
@@ -1216,7 +1229,7 @@ int line_factor(vtk_prec *M) {
     if (jn) HIPCHK(c, hipMemcpyAsync(ext.p, hx.data(), hx.size() * 8, hipMemcpyHostToDevice, c->stream));
     {
         Prof pf(c, "line_setup", -1, 24.0 * (double)A->n_local + matrix_bytes(A));
-        HIPCHK(c, launch_line_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, M->line,
+        HIPCHK(c, launch_line_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, L,
                                     bad.as<unsigned long long>(), ext.as<unsigned long long>(), c->stream));
     }
     if (c->prof_on) prof_flush(c);
@@ -1224,7 +1237,8 @@ int line_factor(vtk_prec *M) {
     HIPCHK(c, hipMemcpyAsync(&br, bad.p, sizeof(br), hipMemcpyDeviceToHost, c->stream));
     if (jn) HIPCHK(c, hipMemcpyAsync(hx.data(), ext.p, hx.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (br != none) return fail(c, VTK_ERR_SINGULAR, "vtk_linejacobi_create: zero or non-finite line pivot at row " + std::to_string(br));
+    bad_row = br;
+    if (br != none) return VTK_OK;
     // x-invariant couplings (every line's a's bit-equal, likewise its c's): the apply forms l and
     // g from a_j, c_j and m (16 B/row read instead of 32); lines without any a (c) take 0
     bool inv = jn > 0;
@@ -1238,15 +1252,46 @@ int line_factor(vtk_prec *M) {
         }
     }
     if (inv) HIPCHK(c, hipMemcpy(acb.p, ac.data(), ac.size() * sizeof(double), hipMemcpyHostToDevice));
-    (void)hipFree(M->line.ac);
-    M->line.ac = nullptr;
-    M->line.compact = 0;
+    (void)hipFree(L.ac);
+    L.ac = nullptr;
+    L.compact = 0;
     if (inv) {
-        M->line.ac = acb.as<double>();
+        L.ac = acb.as<double>();
         acb.p = nullptr;   // owned by the preconditioner now
-        M->line.compact = M->compact_req == 0 ? 0 : 1;
+        L.compact = compact_req == 0 ? 0 : 1;
     }
-    M->line_compact_ok = inv;
+    compact_ok = inv;
+    return VTK_OK;
+}
+
+// The same as bj_factor for line Jacobi (vtk_linejacobi_create / vtk_prec_refresh).
+// VTK_ERR_SINGULAR: a zero or non-finite pivot.
+int line_factor(vtk_prec *M) {
+    unsigned long long br = ~0ull;
+    TRY(line_factor_op(M->A, M->line, M->compact_req, M->line_compact_ok, br));
+    if (br != ~0ull)
+        return fail(M->A->ctx, VTK_ERR_SINGULAR, "vtk_linejacobi_create: zero or non-finite line pivot at row " + std::to_string(br));
+    return VTK_OK;
+}
+
+// The line product (vtk_lineproduct_create / vtk_prec_refresh): both directions' factors and
+// constant-coupling checks, and D = A's diagonal.  VTK_ERR_SINGULAR: a zero or non-finite pivot in
+// either direction (the smaller row is reported).
+int line2_factor(vtk_prec *M) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    unsigned long long br1 = ~0ull, br2 = ~0ull;
+    TRY(line_factor_op(A, M->line, -1, M->line_compact_ok, br1));
+    TRY(line_factor_op(A, M->line2, -1, M->line2_compact_ok, br2));
+    {
+        Prof pf(c, "line2_diag", -1, 8.0 * (double)A->n_local + matrix_bytes(A));
+        HIPCHK(c, launch_line2_diag(A->d_indptr, A->d_indices, A->d_data, A->fp32, A->n_local, M->d_diag, c->stream));
+    }
+    if (c->prof_on) prof_flush(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const unsigned long long br = std::min(br1, br2);
+    if (br != ~0ull)
+        return fail(c, VTK_ERR_SINGULAR, "vtk_lineproduct_create: zero or non-finite line pivot at row " + std::to_string(br));
     return VTK_OK;
 }
 
@@ -1417,8 +1462,11 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
     // line Jacobi with segments <= 32 (register sweeps): dots fused into the sweep kernel
     const bool line_dc = s.M && s.M->kind == VTK_PREC_LINE && s.M->line.seg >= 1 &&
                          s.M->line.seg <= 32 && s.G <= GMAX;
+    // line product: SpMV, sweep 1 in place, sweep 2 with the dots (tuning line2_dc)
+    const bool line2_step = s.M && s.M->kind == VTK_PREC_LINE2 && s.M->line2.seg >= 1 && s.M->line2.seg <= 32 &&
+                            s.G <= GMAX;
     // line path on a line-separable operator: the SpMV from the tables (VTK_BAND_LSV=0: SELL)
-    const bool line_lsv = line_dc && line_lsv_ok(c, s.A);
+    const bool line_lsv = (line_dc || line2_step) && line_lsv_ok(c, s.A);
     const Tiles *ft = s.M ? &s.M->tiles : &s.A->tiles;
     const double b_csr = matrix_bytes(s.A);
     const double b_lsv = b_csr - 8.0 * (double)s.A->sell.entries + 8.0 * (double)n;
@@ -1538,11 +1586,11 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
             const SpmvIn in = lsv_in(spmv_in(s.A, ft, pj), s.A);
             SOFT(launch_spmv_dc(in, s.w, bj_op(s.M), s.V, s.ld, j, s.dcpart, stop, j, c->stream));
             cnt = spmv_grid(in);
-        } else if (line_dc) {
+        } else if (line_dc || line2_step) {
             // line path: SpMV, then the line sweeps with the step's dots fused behind them
             TRY(halo_exchange(s.A, pj));
             const LineOp &lo = s.M->line;
-            if (line_canon && line_fuse_ok(c, s.A, s.M)) {
+            if (line_dc && line_canon && line_fuse_ok(c, s.A, s.M)) {
                 // one rank: the SpMV inside the sweep kernel (y never stored)
                 Prof pf(c, "line_dc", j, b_inv + 8.0 * (double)n + n8 * (j + 2));   // m, D, p, w, V_j
                 SOFT(launch_line_spmv_dc(lo, s.A->d_lsv, pj, s.w, s.V, s.ld, j, s.dcpart, s.G, stop, j, c->stream));
@@ -1559,7 +1607,21 @@ int dcgs2_cycle(Solver &s, const int *stop, volatile int *mirror, hipEvent_t *ev
                 SOFT(launch_spmv(spmv_in(s.A, &s.A->tiles, pj), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr,
                                       nullptr, stop, j, c->stream));
             }
-            if (!cnt) {
+            if (line2_step) {
+                const LineOp &l2 = s.M->line2;
+                {   // t = M1^-1 y in place on the SpMV's output
+                    Prof pf(c, "line_apply", j, line_row_bytes(lo) * n + 2 * n8);
+                    SOFT(launch_line_apply(lo, s.tmp, s.tmp, nullptr, nullptr, nullptr, s.G, stop, j, c->stream));
+                }
+                if (c->tune.line2_dc) {
+                    Prof pf(c, "line2_dc", j, (line_row_bytes(l2) + 8.0) * n + n8 * (j + 3));   // t, D, m, w, p, V_j
+                    SOFT(launch_line2_dc(l2, s.M->d_diag, s.tmp, s.w, s.V, s.ld, j, pj, s.dcpart, s.G, stop, j, c->stream));
+                    cnt = s.G;
+                } else {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
+                    Prof pf(c, "line2_sweep", j, (line_row_bytes(l2) + 8.0) * n + 2 * n8);
+                    SOFT(launch_line2_apply(l2, s.M->d_diag, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream));
+                }
+            } else if (!cnt) {
                 Prof pf(c, "line_dc", j, b_inv + n8 * (j + 3));   // r, m, w, p, V_j
                 SOFT(launch_line_dc(s.M->line, s.tmp, s.w, s.V, s.ld, j, pj, s.dcpart, s.G, stop, j, c->stream));
                 cnt = s.G;
@@ -2813,6 +2875,49 @@ int vtk_linejacobi_create(vtk_csr *A, int64_t stride, int64_t seg, vtk_prec **ou
     return VTK_OK;
 }
 
+int vtk_lineproduct_create(vtk_csr *A, int64_t stride1, int64_t seg1, int64_t stride2, int64_t seg2, vtk_prec **out) {
+    if (!A || !out) return VTK_ERR_ARG;
+    vtk_ctx *c = A->ctx;
+    *out = nullptr;
+    if (stride1 < 1 || seg1 < 1 || stride2 < 1 || seg2 < 1)
+        return fail(c, VTK_ERR_ARG, "vtk_lineproduct_create: strides and segs must be >= 1");
+    if (A->n_global > 1 && (stride1 >= A->n_global || stride2 >= A->n_global))
+        return fail(c, VTK_ERR_ARG, "vtk_lineproduct_create: the strides must be below n (no line has two rows)");
+    HIPCHK(c, hipSetDevice(c->device));
+    auto *M = new vtk_prec();
+    struct Guard { vtk_prec *&m; ~Guard() { if (m) vtk_prec_destroy(m); } } g{M};
+    M->A = A;
+    M->device = c->device;
+    M->kind = VTK_PREC_LINE2;
+    M->bs = 0;
+    const int64_t n1 = std::max<int64_t>(A->n_local, 1);
+    M->line = line_plan(A->n_local, A->row_begin, stride1, seg1);
+    M->line2 = line_plan(A->n_local, A->row_begin, stride2, seg2);
+    HIPCHK(c, hipMalloc(&M->line.f, 3 * n1 * sizeof(double)));
+    HIPCHK(c, hipMalloc(&M->line2.f, 3 * n1 * sizeof(double)));
+    HIPCHK(c, hipMalloc(&M->d_diag, n1 * sizeof(double)));
+    TRY(line2_factor(M));
+    M->epoch = A->values_epoch;
+    *out = M;
+    M = nullptr;
+    return VTK_OK;
+}
+
+int vtk_lineproduct_factors(vtk_prec *M, int which, double *f, int kind) {
+    if (!M || !f) return VTK_ERR_ARG;
+    vtk_ctx *c = M->A->ctx;
+    if (M->kind != VTK_PREC_LINE2) return fail(c, VTK_ERR_STATE, "vtk_lineproduct_factors: not a line-product preconditioner");
+    if (which < 0 || which > 2) return fail(c, VTK_ERR_ARG, "vtk_lineproduct_factors: which must be 0, 1 (l|m|g of a direction) or 2 (D)");
+    TRY(prec_usable(M, "vtk_lineproduct_factors"));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t n = M->A->n_local;
+    const double *src = which == 0 ? M->line.f : which == 1 ? M->line2.f : M->d_diag;
+    if (n > 0)
+        HIPCHK(c, hipMemcpy(f, src, (which == 2 ? 1 : 3) * n * sizeof(double), kind == VTK_PTR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return VTK_OK;
+}
+
 int vtk_linejacobi_factors(vtk_prec *M, double *f, int kind) {
     if (!M || !f) return VTK_ERR_ARG;
     vtk_ctx *c = M->A->ctx;
@@ -2927,7 +3032,7 @@ int vtk_prec_refresh(vtk_prec *M, int64_t *epoch) {
     HIPCHK(c, hipSetDevice(c->device));
     // the factors are overwritten from the first launch on: M is invalid until they are whole again
     const int64_t e = A->values_epoch;
-    const int rc = M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
+    const int rc = M->kind == VTK_PREC_LINE2 ? line2_factor(M) : M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
     if (rc == VTK_ERR_SINGULAR) M->valid = false;
     if (rc != VTK_OK) return rc;
     M->valid = true;
@@ -2969,7 +3074,7 @@ int vtk_bjacobi_apply(vtk_prec *M, const double *r, double *z, int kind) {
     TRY(stage_in(c, r, n, kind, sr));
     TRY(stage_in(c, kind == VTK_PTR_DEVICE ? z : nullptr, n, kind, sz));
     {
-        Prof pf(c, M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply", -1, bj_row_bytes(M) * n + 16.0 * n);
+        Prof pf(c, prec_cls(M), -1, bj_row_bytes(M) * n + 16.0 * n);
         HIPCHK(c, launch_bj_apply(bj_op(M), n, sr.d, sz.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0, c->stream));
     }
     if (c->prof_on) prof_flush(c);
@@ -3038,6 +3143,9 @@ void vtk_prec_destroy(vtk_prec *M) {
     (void)hipFree(M->d_tri);
     (void)hipFree(M->line.f);
     (void)hipFree(M->line.ac);
+    (void)hipFree(M->line2.f);
+    (void)hipFree(M->line2.ac);
+    (void)hipFree(M->d_diag);
     free_tiles(M->tiles);
     free_tiles(M->tiles_in);
     free_tiles(M->tiles_bd);

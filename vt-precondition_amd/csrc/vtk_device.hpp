@@ -201,6 +201,32 @@ __device__ __forceinline__ bool stopped(const int *stop_col, int col) {
     return stop_col != nullptr && __builtin_nontemporal_load(stop_col) < col;
 }
 
+// line sweeps (k_line_setup / k_line_apply, vtk_kernels.hip; k_line2_apply, vtk_line2.hip):
+// wavefront item t -> the segment's line range [i_beg, i_end) and this lane's j (jv: in range)
+struct LineLane {
+    int64_t i_beg, i_end, j;
+    bool jv;
+};
+__device__ __forceinline__ LineLane line_lane(const LineOp &L, int64_t t, int lane) {
+    const int64_t k = t / L.jb, jw = t - k * L.jb;
+    const int64_t s = L.i_lo / L.seg + k;
+    LineLane o;
+    o.i_beg = s * L.seg > L.i_lo ? s * L.seg : L.i_lo;
+    o.i_end = (s + 1) * L.seg < L.i_hi + 1 ? (s + 1) * L.seg : L.i_hi + 1;
+    const int64_t jj = jw * 64 + lane;
+    o.jv = jj < L.jn;
+    o.j = L.j0 + jj;
+    return o;
+}
+// the DCGS2 step's operands of a sweep kernel with the dots fused behind it (DCD)
+struct LineDc {
+    const double *V;
+    int64_t ld;
+    int j;
+    const double *p;
+    double *part;
+};
+
 // The basis vector an MGS step subtracts (and the basis read by the x update) is loaded
 // non-temporal, 16 B per lane, so that w stays resident in the 256 MB Infinity Cache across
 // the chain of MGS kernels: on C3 (20M rows) an MGS step went from 122 us to 98 us

@@ -235,6 +235,8 @@ struct Tuning {
     int g4_gr = 512;          // k_g4_ring: rows per group = lanes per workgroup (256 | 512)
     int g4_fast = 1;          // (A/B) k_g4_ring's straight-line sum for waves of inner rows
     int line_fuse = 1;        // line path (one rank, canonical rows): the SpMV inside the sweep kernel
+    int line2_dc = 1;         // line product, DCGS2 step: the dots fused behind the second sweep
+                              // (0: the plain second sweep, then launch_dc_dots; A/B and tests)
     int cyc_ring = 512;       // > 0: cycle-start residual and DCGS2 step 0 through the x-line ring
                               // (k_lsv_ring_epi, ~that many workgroups; 2D line-separable rows)
     int bcg_fuse = 1;         // BiCGStab with BJ, bs in {1, 2, 4, 8}: phat = M p and shat = M s inside
@@ -365,6 +367,11 @@ struct vtk_prec {
     int kind = VTK_PREC_BJACOBI;
     vtk::LineOp line;
     bool line_compact_ok = false;   // x-invariant couplings found at setup (line.ac valid)
+    // line product (vtk_lineproduct_create): kind VTK_PREC_LINE2, M = M1 D^-1 M2 with M1 = line,
+    // M2 = line2 and d_diag = D, A's diagonal (n doubles)
+    vtk::LineOp line2;
+    bool line2_compact_ok = false;
+    double *d_diag = nullptr;
     // vtk_prec_refresh: what creation was asked for, and the operator values the
     // factors were computed from
     int setup = VTK_BJ_SETUP_EXACT;  // resolved vtk_bj_setup (EXACT or MFMA)
@@ -407,6 +414,10 @@ struct BjOp {
     int64_t tri_ld = 0;
     int bs = 0;
     const LineOp *line = nullptr;   // line Jacobi instead (inv/tri unused)
+    // line product (vtk_lineproduct_create): z = M2^-1 (D (M1^-1 r)) with M1 = line,
+    // M2 = line2 and D = diag (A's diagonal, n doubles)
+    const LineOp *line2 = nullptr;
+    const double *diag = nullptr;
 };
 
 // mm[0] = min, mm[1] = max of idx[0..n) (mm preset to INT_MAX, INT_MIN)
@@ -458,6 +469,16 @@ hipError_t launch_line_spmv_dc(const LineOp &L, const double *lsv, const double 
                                int64_t ld, int j, double *part, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_line_apply(const LineOp &L, const double *r, double *z, const double *v0, double *part0,
                              double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+// line product, second sweep (vtk_line2.hip): z = M_L^-1 (D t), the forward sweep's right-hand side
+// formed as D[k] t[k] per row; t and z may alias.  Partials as launch_line_apply / launch_line_dc
+// (the DCD form: segments <= 32, else hipErrorInvalidValue).  launch_line2_diag: D[r] = the sum of
+// row r's stored entries with col == row, in stored order from 0.0 (k_line_setup's b)
+hipError_t launch_line2_diag(const int32_t *indptr, const int32_t *indices, const void *data, int fp32, int64_t n,
+                             double *D, hipStream_t s);
+hipError_t launch_line2_apply(const LineOp &L, const double *D, const double *t, double *z, const double *v0,
+                              double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, double *w, const double *V, int64_t ld,
+                           int j, const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_bj_tri_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
                                int64_t n, int bs, const double *inv, double *tri, int64_t ld, int *flags,
                                hipStream_t s);

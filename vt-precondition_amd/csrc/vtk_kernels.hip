@@ -1153,6 +1153,12 @@ __global__ __launch_bounds__(NT) void k_bj_apply_tri(const double *__restrict__ 
 hipError_t launch_bj_apply(const BjOp &bj, int64_t n, const double *r, double *z,
                            const double *v0, double *part0, double *part1, int grid,
                            const int *stop_col, int col, hipStream_t s) {
+    if (bj.line && bj.line2) {
+        // line product: t = M1^-1 r into z, then z = M2^-1 (D t) in place
+        const hipError_t e = launch_line_apply(*bj.line, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, s);
+        if (e != hipSuccess) return e;
+        return launch_line2_apply(*bj.line2, bj.diag, z, z, v0, part0, part1, grid, stop_col, col, s);
+    }
     if (bj.line) return launch_line_apply(*bj.line, r, z, v0, part0, part1, grid, stop_col, col, s);
     if (n == 0 && part0 == nullptr) return hipSuccess;
     if (bj.tri) {
@@ -1276,22 +1282,8 @@ LineOp line_plan(int64_t n, int64_t row0, int64_t stride, int64_t seg) {
     return L;
 }
 
-// wavefront item t -> the segment's line range [i_beg, i_end) and this lane's j (jv: in range)
-struct LineLane {
-    int64_t i_beg, i_end, j;
-    bool jv;
-};
-__device__ __forceinline__ LineLane line_lane(const LineOp &L, int64_t t, int lane) {
-    const int64_t k = t / L.jb, jw = t - k * L.jb;
-    const int64_t s = L.i_lo / L.seg + k;
-    LineLane o;
-    o.i_beg = s * L.seg > L.i_lo ? s * L.seg : L.i_lo;
-    o.i_end = (s + 1) * L.seg < L.i_hi + 1 ? (s + 1) * L.seg : L.i_hi + 1;
-    const int64_t jj = jw * 64 + lane;
-    o.jv = jj < L.jn;
-    o.j = L.j0 + jj;
-    return o;
-}
+// (LineLane / line_lane, the wavefront item -> segment map, and LineDc live in vtk_device.hpp:
+// vtk_line2.hip's second sweep uses the same decomposition)
 
 // Thomas factors along the lane's line segment: u = b | l = a m_prev, u = b - l c_prev;
 // m = 1 / u; g = c m.  A row's "previous" is the lane's previous valid row (rows of one (j,
@@ -1376,13 +1368,6 @@ __global__ __launch_bounds__(NT) void k_line_setup(const int32_t *__restrict__ i
 // lane's registers, p and the basis rows of the lane's segment rows are read once here:
 // s = V_j^T p, z = V_j^T w, ||p||^2, p.w, ||w||^2 as per-workgroup partials in launch_dc_dots'
 // layout (dc.part[q * GMAX + block]); no separate dots kernel re-reads w.
-struct LineDc {
-    const double *V;
-    int64_t ld;
-    int j;
-    const double *p;
-    double *part;
-};
 template <int LMAX, bool COMPACT, bool DCD = false>
 __global__ __launch_bounds__(NT) void k_line_apply(LineOp L, const double *r, double *z,
                                                    const double *__restrict__ v0, double *part0,

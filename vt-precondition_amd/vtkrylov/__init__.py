@@ -29,7 +29,8 @@ from ._abi import check, lib
 
 __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "vlasov_operator", "block_jacobi",
            "gmres", "VlasovParams", "vlasov_params", "rhs_splitmix", "partition_rows",
-           "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi",
+           "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi", "line_product", "LineProduct",
+           "vlasov_line_directions",
            "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats",
            "ArnoldiCapture", "last_arnoldi"]
 
@@ -328,8 +329,10 @@ class CsrOperator:
 
     def precond_matvec(self, M, x):
         """w = M^-1 (A x) through the launch the solver's split DCGS2 step uses for this operator
-        (SciPy: ``M.matvec(A @ x)``; vtk_precond_matvec).  M: a BlockJacobi / LineJacobi of this
-        operator, or None (w = A x)."""
+        (SciPy: ``M.matvec(A @ x)``; vtk_precond_matvec).  M: a BlockJacobi / LineJacobi /
+        LineProduct of this operator, or None (w = A x)."""
+        if M is not None and not isinstance(M, _PRECS):
+            raise TypeError("CsrOperator.precond_matvec: M must be " + _PRECS_TEXT)
         vx = _Vec(x, self.n_local)
         mh = M.handle if M is not None else None
         if vx.kind == _abi.PTR_DEVICE:
@@ -750,6 +753,84 @@ def vlasov_line_stride(params) -> int:
     return sh[1] * sh[2] * sh[3]
 
 
+def vlasov_line_directions(params) -> list[int]:
+    """The line strides of a Vlasov operator, strongest advection direction first: [1] (1D),
+    [Nv, 1] (2D: x, then v), [Ny*Nvx*Nvy, Nvx*Nvy] (4D: x, then y).  The first entry is
+    :func:`vlasov_line_stride`; the first two are :func:`line_product`'s directions."""
+    dim = int(params.dim)
+    sh = [int(v) for v in params.shape]
+    if dim == 1:
+        return [1]
+    if dim == 2:
+        return [sh[1], 1]
+    return [sh[1] * sh[2] * sh[3], sh[2] * sh[3]]
+
+
+class LineProduct:
+    """Two-direction line preconditioner: the approximate-factorisation product
+    M = M1 D^-1 M2 = D + X + Y + X D^-1 Y of two :class:`LineJacobi` matrices of ``A``, given as
+    ``(stride, seg)`` pairs, with D = A's diagonal.  SciPy statement:
+    ``LinearOperator(matvec=lambda r: lu2.solve(D * lu1.solve(r)))`` with ``lu_i = splu(M_i)``.
+    ``vtk_lineproduct_create``.
+
+    For the 4D Vlasov operators the directions are x and y: :func:`vlasov_line_directions`."""
+
+    def __init__(self, A: CsrOperator, dir1, dir2):
+        (s1, g1), (s2, g2) = dir1, dir2
+        h = C.c_void_p()
+        check(lib().vtk_lineproduct_create(A.handle, int(s1), int(g1), int(s2), int(g2), C.byref(h)), A.ctx.handle)
+        self._h = h
+        self.A = A
+        self.directions = ((int(s1), int(g1)), (int(s2), int(g2)))
+        self.shape = A.shape
+        self.dtype = np.dtype(np.float64)
+        self._epoch = A.values_epoch
+
+    def refresh(self):
+        """Recompute both directions' Thomas factors and D from the operator's current values and
+        re-run the constant-coupling check per direction (``vtk_prec_refresh``).  LinAlgError on a
+        zero pivot -- unusable (VtkError, status ERR_STATE) until a later refresh succeeds."""
+        return _refresh(self)
+
+    @property
+    def values_epoch(self) -> int:
+        """``A.values_epoch`` of the values the factors were computed from."""
+        return self._epoch
+
+    @property
+    def handle(self):
+        return self._h
+
+    def factors(self, which: int) -> np.ndarray:
+        """l | m | g of direction ``which`` (0 or 1), 3 * n_local doubles (the oracle's
+        orc_line_setup layout)."""
+        if which not in (0, 1):
+            raise ValueError("LineProduct.factors: which must be 0 or 1")
+        f = np.empty(3 * self.A.n_local)
+        check(lib().vtk_lineproduct_factors(self._h, int(which), _np_ptr(f), _abi.PTR_HOST), self.A.ctx.handle)
+        return f
+
+    def diagonal(self) -> np.ndarray:
+        """D: per row the sum of its stored diagonal entries (n_local doubles)."""
+        d = np.empty(self.A.n_local)
+        check(lib().vtk_lineproduct_factors(self._h, 2, _np_ptr(d), _abi.PTR_HOST), self.A.ctx.handle)
+        return d
+
+    matvec = LineJacobi.matvec
+    __matmul__ = LineJacobi.__matmul__
+    close = LineJacobi.close
+    __del__ = LineJacobi.__del__
+
+
+def line_product(A: CsrOperator, dir1, dir2) -> LineProduct:
+    """``line_product(A, (stride1, seg1), (stride2, seg2))``: see :class:`LineProduct`."""
+    return LineProduct(A, dir1, dir2)
+
+
+_PRECS = (BlockJacobi, LineJacobi, LineProduct)
+_PRECS_TEXT = "None, vtkrylov.BlockJacobi, vtkrylov.LineJacobi or vtkrylov.LineProduct"
+
+
 @dataclass
 class SolveStats:
     inner_iters: int
@@ -837,7 +918,7 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     modified Gram-Schmidt sequence (iterative.py:755-759); ``orth="dcgs2"`` forces DCGS2.
 
     ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
-    :class:`BlockJacobi` or a :class:`LineJacobi` built on ``A``; any other preconditioner raises TypeError (no CPU
+    :class:`BlockJacobi`, a :class:`LineJacobi` or a :class:`LineProduct` built on ``A``; any other preconditioner raises TypeError (no CPU
     fallback).  ``callback`` is not supported (the Arnoldi loop never returns to the host).
     ``restart``/``maxiter``: None = SciPy's defaults (20 / 10 n); explicit values must be
     positive integers (ValueError otherwise).
@@ -846,8 +927,8 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     if callback is not None:
         raise NotImplementedError("vtkrylov.gmres: callbacks would force a host round trip per "
                                   "Arnoldi step and are not supported")
-    if M is not None and not isinstance(M, (BlockJacobi, LineJacobi)):
-        raise TypeError("vtkrylov.gmres: M must be None, vtkrylov.BlockJacobi or vtkrylov.LineJacobi")
+    if M is not None and not isinstance(M, _PRECS):
+        raise TypeError("vtkrylov.gmres: M must be " + _PRECS_TEXT)
     if not isinstance(A, CsrOperator):
         A = csr_matrix(A)
     if atol == "legacy" or atol is None or atol < 0:
@@ -925,7 +1006,7 @@ def bicgstab(A, b, x0=None, *, rtol=1e-5, atol=0., maxiter=None, M=None, callbac
     same point; the communicator stays usable.
 
     ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
-    :class:`BlockJacobi` or a :class:`LineJacobi` built on ``A``; any other preconditioner raises
+    :class:`BlockJacobi`, a :class:`LineJacobi` or a :class:`LineProduct` built on ``A``; any other preconditioner raises
     TypeError (no CPU fallback).  ``callback`` is not supported (the loop never returns to the
     host).  ``maxiter``: None = SciPy's default (10 n); an explicit value must be a positive integer.
     """
@@ -933,8 +1014,8 @@ def bicgstab(A, b, x0=None, *, rtol=1e-5, atol=0., maxiter=None, M=None, callbac
     if callback is not None:
         raise NotImplementedError("vtkrylov.bicgstab: callbacks would force a host round trip per "
                                   "iteration and are not supported")
-    if M is not None and not isinstance(M, (BlockJacobi, LineJacobi)):
-        raise TypeError("vtkrylov.bicgstab: M must be None, vtkrylov.BlockJacobi or vtkrylov.LineJacobi")
+    if M is not None and not isinstance(M, _PRECS):
+        raise TypeError("vtkrylov.bicgstab: M must be " + _PRECS_TEXT)
     if atol == "legacy" or atol is None or atol < 0:
         raise ValueError(f"'scipy.sparse.linalg.bicgstab' called with invalid `atol`={atol}; "
                          "if set, `atol` must be a real, non-negative number.")

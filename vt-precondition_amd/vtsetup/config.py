@@ -76,6 +76,10 @@ class SolverConfig:
     gpus: int = 1                 # run/gpus: ranks, one process per GPU (absent: 1)
     comm: str = "rccl"            # run/comm: rccl, or host (host-staged, ranks may share a GPU)
     method: str = "gmres"         # solver/method: gmres, or bicgstab (one rank; absent: gmres)
+    # preconditioner type line_product: the second direction (optional nodes; 0 = absent: the second
+    # entry of vtkrylov.vlasov_line_directions, and line_segment)
+    line_stride2: int = 0
+    line_segment2: int = 0
 
     @classmethod
     def load(cls, path: str = DEFAULT_XML, **overrides) -> "SolverConfig":
@@ -105,10 +109,12 @@ class SolverConfig:
         cfg.gpus = int(t.get_optional("run/gpus", "1") or 1)
         cfg.comm = (t.get_optional("run/comm", "rccl") or "rccl").lower()
         cfg.method = (t.get_optional("solver/method", "gmres") or "gmres").lower()
+        cfg.line_stride2 = int(t.get_optional("preconditioner/line_stride2", "0") or 0)
+        cfg.line_segment2 = int(t.get_optional("preconditioner/line_segment2", "0") or 0)
         for k, v in overrides.items():
             if v is not None:
                 setattr(cfg, k, v)
-        if cfg.preconditioner not in ("block_jacobi", "line_jacobi", "none"):
+        if cfg.preconditioner not in ("block_jacobi", "line_jacobi", "line_product", "none"):
             raise ValueError(f"unknown preconditioner {cfg.preconditioner!r}")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")

@@ -97,6 +97,18 @@ class KrylovPrecondition:
                     stride = vk.vlasov_line_stride(vk.vlasov_params(c.dim, c.shape))
             self.M = vk.line_jacobi(self.A, stride, c.line_segment)
             info.update(line_stride=stride, line_segment=c.line_segment)
+        elif c.preconditioner == "line_product":
+            # two line directions (vtkrylov.line_product): x, then the second entry of
+            # vlasov_line_directions unless preconditioner/line_stride2 names it
+            dirs = [] if c.operator_file else vk.vlasov_line_directions(vk.vlasov_params(c.dim, c.shape))
+            stride = c.line_stride if c.line_stride > 0 else (dirs[0] if dirs else self.A.line_band)
+            stride2 = c.line_stride2 if c.line_stride2 > 0 else (dirs[1] if len(dirs) > 1 else 0)
+            if stride <= 0 or stride2 <= 0:
+                raise ValueError("line_product needs two line directions: set preconditioner/line_stride and "
+                                 "preconditioner/line_stride2 (an operator file, or a 1D operator, has no second one)")
+            seg2 = c.line_segment2 if c.line_segment2 > 0 else c.line_segment
+            self.M = vk.line_product(self.A, (stride, c.line_segment), (stride2, seg2))
+            info.update(line_stride=stride, line_segment=c.line_segment, line_stride2=stride2, line_segment2=seg2)
         info["t_setup_s"] = self._max(time.perf_counter() - t)
         self.result["preconditioner"] = info
 
@@ -259,7 +271,7 @@ def test_main(argv=None) -> int:
     ap.add_argument("--config")
     ap.add_argument("--report")
     ap.add_argument("--operator-file", help="SciPy save_npz CSR archive to solve")
-    ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "none"])
+    ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "line_product", "none"])
     ap.add_argument("--orth", choices=["auto", "mgs", "dcgs2"])
     ap.add_argument("--method", choices=["gmres", "bicgstab"], help="solver (overrides solver/method)")
     ap.add_argument("--gpus", type=int, help="ranks (overrides run/gpus)")
