@@ -23,7 +23,7 @@ def _free_port():
 
 
 class DistOps:
-    """Distributed SpMV / BJ / dot of one rank, mirroring vtk_api.cpp's multi-rank schedule."""
+    """Distributed SpMV / BJ / dot of one rank, mirroring the library's multi-rank schedule (vtk_driver.hpp, vtk_gmres.cpp)."""
 
     def __init__(self, vk, dist, p, offs, rank, world, prec="bj", seg=0):
         from oracle import coracle
@@ -34,7 +34,7 @@ class DistOps:
         self.loc, self.halo_cols, self.recv_cnt = vk.halo_plan(p.n, offs, rank, ix)
         self.loc = self.loc.astype(np.int32)
         # everyone learns what it must send (counts allgather), then the requested ids travel
-        # to their owners (alltoallv) — setup_halo() in vtk_api.cpp
+        # to their owners (alltoallv) — setup_halo() in vtk_operator.cpp
         import torch
         cnt = torch.from_numpy(self.recv_cnt.astype(np.int64))
         allc = [torch.empty(world, dtype=torch.int64) for _ in range(world)]

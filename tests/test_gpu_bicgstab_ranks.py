@@ -24,7 +24,7 @@ from test_gpu_bicgstab import ref as ref_one_rank
 
 pytestmark = pytest.mark.gpu
 
-LOOKAHEAD = 3   # iterations the host enqueues ahead of the device (vtk_api.cpp)
+LOOKAHEAD = 3   # iterations the host enqueues ahead of the device (vtk_driver.hpp)
 KINDS = [("none", "auto"), ("bj8", "auto"), ("bj8", "inverse"), ("bj16", "auto"), ("line", "auto")]
 RTOLS = [1e-5, 1e-8]
 

@@ -95,7 +95,7 @@ template <int OPT> __device__ __forceinline__ void band_sync() {
 constexpr int BAND_OFF = 16;
 // OPT bit 6 (ND, canonical rows): no read of the diagonal table D.  The band step runs only with the
 // tridiagonal BJ(8) factors of A's current diagonal blocks (bj_op() hands out tri for the operator's
-// current values_epoch only; the launch site in vtk_api.cpp states the guard), so A = M + C with C
+// current values_epoch only; the launch site in vtk_gmres.cpp states the guard), so A = M + C with C
 // the x +- 1 couplings and the v +- 1 couplings that cross an 8-row block edge, and
 //   w = M^-1 A p = p + M^-1 (C p):
 // the row sum y = C p skips the diagonal and the in-block v +- 1 products (the in-block couplings

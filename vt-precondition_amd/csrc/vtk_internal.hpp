@@ -1,4 +1,4 @@
-// vtk_internal.hpp — types shared by the C-ABI/driver (vtk_api.cpp, vtk_host.cpp) and the
+// vtk_internal.hpp — types shared by the host units (listed in vtk_driver.hpp) and vtk_host.cpp, and the
 // gfx950 kernels (vtk_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <cmath>
@@ -406,7 +406,7 @@ struct SpmvIn {
 LineOp line_plan(int64_t n, int64_t row0, int64_t stride, int64_t seg);
 
 // block-Jacobi operator as the kernels see it: inverse rows f64[nb][bs][bs], or (tri != null)
-// the LU factors of tridiagonal blocks, SoA l | m | g with stride tri_ld (vtk_api.cpp, BJ
+// the LU factors of tridiagonal blocks, SoA l | m | g with stride tri_ld (vtk_driver.hpp bj_op, BJ
 // modes).  bs == 0: identity.
 struct BjOp {
     const double *inv = nullptr;

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
 
 // ------------------------------------------------------------------------------------------
 // CSR SpMV in the SELL-64 layout (built on the device from the CSR when its padding is small,
-// vtk_api.cpp): one wavefront per 64-row chunk, lane l = row 64q+l, entries column-major in the
+// vtk_operator.cpp): one wavefront per 64-row chunk, lane l = row 64q+l, entries column-major in the
 // chunk.  Every lane sums its row's products serially in stored order (padding skipped), so y
 // is bit-identical to csr_matvec and to k_spmv.  No LDS and no barriers on the SpMV itself; a
 // workgroup takes a group of 4 chunks (256 contiguous rows).  col/val are streamed once:
