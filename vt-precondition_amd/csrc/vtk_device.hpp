@@ -1,5 +1,5 @@
 // vtk_device.hpp — device helpers shared by the gfx950 kernel translation units
-// (vtk_kernels.hip, vtk_band.hip): deterministic wave / workgroup reductions, DPP lane moves,
+// (vtk_kernels.hip, vtk_band.hip, vtk_ring.hip): deterministic wave / workgroup reductions, DPP lane moves,
 // non-temporal load/store wrappers, the tridiagonal block-Jacobi group solves, the Hessenberg
 // back substitution and the DCGS2 x update.  Device code only; not part of the public ABI.
 #pragma once
@@ -55,10 +55,47 @@ __device__ __forceinline__ int canon_order(int64_t r, int64_t n, int L, int X, i
                                            int xord = 0) {
     return canon_order_xv(r / L, r % L, n, L, X, lblk, cxm, cxp, xord);
 }
+// the three orders canon_order_xv returns for a slab of X >= 2 lines: an interior line, one rank's
+// first line (x - 1 wraps: last) and its last line (x + 1 wraps: first); across ranks xord picks among
+// the same three.  (A fourth, 4 1 2 3 0, needs a one-line slab that is both the first and the last.)
+constexpr int P_MID = 0 | 1 << 3 | 2 << 6 | 3 << 9 | 4 << 12;
+constexpr int P_FIRST = 1 | 2 << 3 | 3 << 6 | 4 << 9 | 0 << 12;
+constexpr int P_LAST = 4 | 0 << 3 | 1 << 6 | 2 << 9 | 3 << 12;
+// the canonical row's sum in the stored order ord (uniform; neither P_MID nor P_FIRST: P_LAST),
+// straight-line: t0 .. t4 are the products of kinds 0 .. 4 (every lane has all five, from a clamped
+// row where a kind is absent), the absent v -+ 1 terms (h1 / h3 false) are skipped by selects --
+// k_sell's additions in k_sell's order, without per-entry branches.  ND (BAND_ND): y = C p -- no
+// diagonal term, the v -+ 1 terms only across an 8-row block edge (ii = row mod 8)
+template <bool ND>
+__device__ __forceinline__ double canon_row_sum(int ord, double t0, double t1, double t2, double t3, double t4,
+                                                bool h1, bool h3, int ii) {
+    const bool c1 = ND ? h1 && ii == 0 : h1, c3 = ND ? h3 && ii == 7 : h3;
+    double sa = 0.0;
+    if (ord == P_MID) {
+        sa = sa + t0;
+        sa = c1 ? sa + t1 : sa;
+        if constexpr (!ND) sa = sa + t2;
+        sa = c3 ? sa + t3 : sa;
+        sa = sa + t4;
+    } else if (ord == P_FIRST) {
+        sa = c1 ? sa + t1 : sa;
+        if constexpr (!ND) sa = sa + t2;
+        sa = c3 ? sa + t3 : sa;
+        sa = sa + t4;
+        sa = sa + t0;
+    } else {
+        sa = sa + t4;
+        sa = sa + t0;
+        sa = c1 ? sa + t1 : sa;
+        if constexpr (!ND) sa = sa + t2;
+        sa = c3 ? sa + t3 : sa;
+    }
+    return sa;
+}
 
 // the entries of canonical row (xl, v) -- row = xl L + v, local numbering, n local rows, X = n / L
 // lines -- in stored order from the line-separable tables lsv = D[n] | TX[2][L] | TV[2][X]
-// (vtk_band.hip k_lsv_build): column c[e] (-1: kind absent at v = 0 / L - 1) and value d[e].
+// (vtk_ring.hip k_lsv_build): column c[e] (-1: kind absent at v = 0 / L - 1) and value d[e].
 // The SELL copy of the same row holds the same columns and values in the same order, padding
 // after them, so a sum over these in order equals the SELL sum bit for bit
 __device__ __forceinline__ void canon_row(const double *__restrict__ lsv, int n, int L, int lblk, int xl, int v,

@@ -32,9 +32,9 @@ struct Solver {
     // (step j's w in the buffer j % 3: the band step reads w_{j-1} and w_j, writes w_{j+1})
     bool band = false;
     int band_G = 0, band_H = 1;
-    int band_G3 = 0;   // grid of the three-workgroups-per-CU launches (band_opt bit 1, j <= BAND_J3)
+    int band_G3 = 0;   // grid of the three-workgroups-per-CU launches (BAND_WPC3, j <= BAND_J3)
     // workgroups (= partials) of the band step launched at step j
-    int band_grid(int j, int opt) const { return (opt & 2) && j <= BAND_J3 && band_G3 > 0 ? band_G3 : band_G; }
+    int band_grid(int j, int opt) const { return (opt & BAND_WPC3) && j <= BAND_J3 && band_G3 > 0 ? band_G3 : band_G; }
     double *w3 = nullptr;
     double *wbuf(int j) const { return j % 3 == 0 ? w : j % 3 == 1 ? tmp : w3; }
     double *ghost = nullptr, *gsend = nullptr, *grecv = nullptr;   // distributed band step
@@ -155,25 +155,25 @@ StepPlan step_plan(const Solver &s) {
     // line-separable values in the band step (tuning band_lsv 0: the SELL values)
     P.band_lsv = s.band && A->d_lsv && c->tune.band_lsv;
     P.band_canon = c->tune.band_canon != 0;       // 0: read the codes anyway (A/B)
-    // the band step's variant bits exist for the line-separable, canonical-row instantiations (one
-    // rank: launch_band_one_rank; across ranks with ghost lines: launch_band_ghost, round 6): every
+    // the band step's variant bits (BandOpt) exist for the line-separable, canonical-row
+    // instantiations (one rank and, since round 6, across ranks with ghost lines): every
     // other launch, and the partial count its successor reads, takes the base grid
-    // bits 3 (the LDS-DMA prefetch of J > BAND_PF) and 4 (the alternating walk) pay only on long
+    // BAND_L2PF (the LDS-DMA prefetch of J > BAND_PF) and BAND_ALT (the alternating walk) pay only on long
     // basis vectors: on smaller ones (C2, the C3 slabs) more of the basis stays in the Infinity
     // Cache between steps, so the DMA's issue and L2 over-fetch cost more than the latency it hides
     // and the halo lines' second read hits anyway (band_long_rows, vtk_internal.hpp)
-    // bit 5 (odd steps walk the other way round) stays at every size: in-process A/B 63 vs 31,
-    // median ms per solve (spread of the eight bit-5-off solves): C3 36.62 vs 37.37 (0.18), C3/2
+    // BAND_SERP (odd steps walk the other way round) stays at every size: in-process A/B 63 vs 31,
+    // median ms per solve (spread of the eight SERP-off solves): C3 36.62 vs 37.37 (0.18), C3/2
     // slab 18.86 vs 18.95 (0.02), C2 10.21 vs 10.28 (0.08), C3/8 slab 6.16 vs 6.23 (0.04)
     // (profiles/serpentine_ab*.json)
-    // bit 6 (no read of the diagonal table, w = p + M^-1 (A - M) p) exists for the same
+    // BAND_ND (no read of the diagonal table, w = p + M^-1 (A - M) p) exists for the same
     // instantiations only: masked off with the others where the rows are not canonical line-separable
     P.band_opt = P.band_lsv && A->lsv_canon && P.band_canon
-                     ? (n >= c->tune.band_long_rows ? c->tune.band_opt : c->tune.band_opt & ~(8 | 16))
+                     ? (n >= c->tune.band_long_rows ? c->tune.band_opt : c->tune.band_opt & ~(BAND_L2PF | BAND_ALT))
                      : 0;
     // the band step's matrix bytes: SELL codes + dictionary + (values: 8 B per row from D, or
-    // the SELL values); with bit 6 no matrix bytes per row at all
-    P.band_nd = (P.band_opt & 64) != 0;
+    // the SELL values); with BAND_ND no matrix bytes per row at all
+    P.band_nd = (P.band_opt & BAND_ND) != 0;
     P.b_band = P.band_lsv ? (A->lsv_canon && P.band_canon
                                  ? (P.band_nd ? 0.0 : 8.0 * (double)n)   // the diagonal only
                                  : P.b_csr - 8.0 * (double)A->sell.entries + 8.0 * (double)n)
@@ -426,11 +426,11 @@ int band_step(Solver &s, const StepPlan &P, int j) {
     a.n = s.n, a.L = (int)A->band_L, a.X = (int)(s.n / A->band_L), a.H_parts = s.band_H;
     a.ghost = s.ghost, a.left_blk = A->band_lblk, a.xord = A->band_xord;
     a.lsv = P.band_lsv ? A->d_lsv : nullptr;
-    a.canon = P.band_lsv && A->lsv_canon && P.band_canon ? 2 : 0;   // 2: the straight-line SpMV per line order
-    // bit 6 computes w = p + M^-1 (A - M) p, which is M^-1 A p only while a.mtri holds the
+    a.canon = P.band_lsv && A->lsv_canon && P.band_canon;
+    // BAND_ND computes w = p + M^-1 (A - M) p, which is M^-1 A p only while a.mtri holds the
     // factors of A's CURRENT diagonal blocks.  band_eligible requires bj8_tri(M), which is false
     // unless M->epoch == A->values_epoch (a lagged M takes the non-band path).  A change that
-    // lets a lagged M reach this launch must clear bit 6 here, or the operator is wrong
+    // lets a lagged M reach this launch must clear BAND_ND here, or the operator is wrong
     a.opt = P.band_opt;
     SOFT(launch_band_step(a, s.band_grid(j, a.opt), A->sell.uniform_w, c->stream));
     return VTK_OK;

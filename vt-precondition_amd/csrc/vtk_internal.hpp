@@ -164,7 +164,7 @@ struct Grid4 {
     const void *D = nullptr;       // diagonal per row, the operator's value type
 };
 inline size_t grid4_tab_len(const Grid4 &g) { return 2 * ((size_t)g.Nvx + g.Nvy + g.X + g.Ny); }
-// k_g4_ring's limits (vtk_band.hip): the LDS table TX | TY | TVX | TVY of <= G4TAB doubles and a
+// k_g4_ring's limits (vtk_ring.hip): the LDS table TX | TY | TVX | TVY of <= G4TAB doubles and a
 // ring of <= 8192 doubles holding the y-line window 2 S3 plus two groups of rows (512 per group for
 // gr >= 512 outside the fused-dots mode 1, else 256).  The solver takes the ring step only for grids
 // that fit (else the SELL grid-row kernels); launch_g4_ring refuses the others
@@ -200,28 +200,13 @@ struct Tuning {
     int band_lsv = 1;         // solver launches read the line-separable values (else SELL values)
     int sell_canon = 1;       // ... and canonical rows' columns from the line index (no codes)
     int band_canon = 1;       // the band step reads no codes on canonical rows
-    int band_opt = 127;       // band step variant bits (vtk_band.hip k_band_step OPT; in-process A/B
-                              // C3: SpMV operands prefetched j00 254 -> 217 us, + three workgroups per
-                              // CU for j <= BAND_J3: j00 190, j01 283 -> 246 us; solve 42.66 -> 42.31 ms;
-                              // round 6: bit 2, a line range's two parts on one XCD: 40.56 -> 40.30 ms;
-                              // bit 3, LDS-DMA L2 prefetch for J > BAND_PF: j13-j18 -21..-50 us each;
-                              // bit 4, odd line ranges walk backwards: 39.98 -> 39.81 ms, C3/8 slab
-                              // 6.652 vs 6.676 ms (neutral).  Since round 6 also across ranks;
-                              // bit 5 (32), odd steps walk the other way round -- a step starts on the
-                              // lines the previous one touched last, still in the Infinity Cache
-                              // (DESIGN.md §3i): C3 37.37 -> 36.62 ms (two runs: -2.0 %, -1.7 %), at
-                              // every size: C2 10.28 -> 10.21, C3/2 slab 18.95 -> 18.86, C3/8 slab
-                              // 6.23 -> 6.16 ms (profiles/serpentine_ab*.json); every step reversed
-                              // instead of every other one: 38.79 vs 38.78 ms, nothing);
-                              // bit 6 (64), no read of the diagonal table: w = p + M^-1 (A - M) p with
-                              // M the tridiagonal BJ(8) of A's current values (the band
-                              // step and step 0 of its cycle; 8 B per row fewer per launch)
-    int band_long_rows = 16000000;   // band_opt bits 3 and 4 only on basis vectors of >= this many rows
-                              // (in-process A/B, round 6: bit 3 on vs off, C3 20M rows 39.30 vs 39.78 ms,
+    int band_opt = 127;       // band step variant bits: every BandOpt bit (below, with each bit's measurements)
+    int band_long_rows = 16000000;   // BAND_L2PF and BAND_ALT only on basis vectors of >= this many rows
+                              // (in-process A/B, round 6: L2PF on vs off, C3 20M rows 39.30 vs 39.78 ms,
                               // C3/2 slab 10M 20.20 vs 20.09, C2 5M 10.98 vs 10.86, C3/8 slab 2.5M 6.53
-                              // vs 6.51; bit 4 on vs off, C3 39.24 vs 39.34, C3/2 20.13 vs 20.00, C3/4
-                              // 11.02 vs 10.95, C2 10.92 vs 10.87).  Bit 5 does not follow it: faster
-                              // at every size measured
+                              // vs 6.51; ALT on vs off, C3 39.24 vs 39.34, C3/2 20.13 vs 20.00, C3/4
+                              // 11.02 vs 10.95, C2 10.92 vs 10.87).  BAND_SERP does not follow it:
+                              // faster at every size measured
     int lsv_ring = 2048;      // > 0: the line path's table SpMV with x staged through LDS, ~that many
                               // workgroups (in-process A/B, C3 line solve: 8.64 -> 8.26 ms; 167 -> 105 us)
     int prof_perj = 0;        // profile class per band step index (band_step_jNN)
@@ -554,6 +539,67 @@ hipError_t launch_dc_update(double *V, int64_t ld, int j, const double *w, int64
                             const DcCoef *cf, int grid, const GmresState *st, double *x,
                             const double *H, const double *S, int m, int nt_pw, hipStream_t s);
 
+// Variant bits of the band step (Tuning::band_opt -> StepPlan::band_opt -> BandK::opt), for the
+// canonical-row kernels (VMODE 2) only: step_plan masks them off elsewhere.  Compile-time bits pick
+// the instantiation (k_band_step's OPT, through vtk_band.hip band_variant); run-time bits are read
+// from a.opt inside the kernel.  All variants compute the same w and partial sums, except: WPC3's
+// grid (more, shorter line ranges), ALT and SERP (a reversed walk sums a range's lines in reverse
+// order) change the dots' summation order, ND the last bits of w -- all within the DCGS2 bars.
+enum BandOpt : int {
+    // compile-time.  With the next-line prefetch (J <= BAND_PF), the SpMV operands of a line (D, m,
+    // the line's v couplings) travel in the same prefetch as the update operands, one line ahead.
+    // Loaded at the head of their own iteration they made the wait for the prefetched update
+    // operands a wait for everything (s_waitcnt vmcnt(0): the loads sit in exec-masked blocks, so
+    // the counter cannot be tracked per load): one exposed memory round trip per line.  (C3: j00 254
+    // -> 217 us.)  Launched only at the step indices where it pays (vtk_band.hip band_spf_j)
+    BAND_SPF = 1,
+    // compile-time, and the host's grid (Solver::band_grid).  Registers capped for 3 workgroups per
+    // CU (6 waves per SIMD) at J <= BAND_J3 (below), whose serial line walks are latency-bound; the
+    // host plans 1.5x the line ranges for them.  (C3, on top of SPF: j00 190, j01 283 -> 246 us;
+    // solve 42.66 -> 42.31 ms)
+    BAND_WPC3 = 2,
+    // run-time.  The two parts of a line range on ONE XCD.  Each part updates one v-halo row on
+    // either side, which lies in the other part's rows: read alone, that row drags its whole 128-B
+    // line from HBM (the band step's PMC fetch is ~9 % over its algorithmic bytes at j >= 9).
+    // Workgroups are dealt to the XCDs round-robin (blockIdx mod 8): vtk_band.hip band_block remaps
+    // them.  (Round 6: 40.56 -> 40.30 ms)
+    BAND_XCDP = 4,
+    // compile-time, J > BAND_PF only (step_plan: long basis vectors only, Tuning::band_long_rows).
+    // The global rows a later line iteration reads -- its update's basis and w rows, its SpMV's D
+    // and m rows -- are touched ahead of time by LDS-DMA loads into a scratch word nobody reads: no
+    // VGPR holds them, so the walk keeps more bytes in flight than the register prefetch alone (one
+    // line ahead without it, J > BAND_PF; two with it).  The barriers then are bare s_barriers
+    // (vtk_band.hip band_sync).  (j13-j18 -21..-50 us each)
+    BAND_L2PF = 8,
+    // run-time (long basis vectors only, as L2PF).  Odd line ranges walk their lines backwards, so
+    // that the two workgroups on either side of every range boundary read the boundary's two lines
+    // (each one's own line and the other's x-halo line) at the same time, at the start or at the
+    // end of both walks: the second read finds the line in the Infinity Cache instead of HBM.
+    // (39.98 -> 39.81 ms, C3/8 slab 6.652 vs 6.676 ms (neutral).  Since round 6 also across ranks)
+    BAND_ALT = 16,
+    // run-time (against the template's J: no cost).  Odd steps walk the other way round, on top of
+    // ALT's range parity, so step j + 1 begins with the lines step j touched last -- the rows it
+    // reads there (V_k, v_j, both w, D, m) were read or written a few hundred MB of traffic earlier
+    // and are still in the Infinity Cache.  The non-temporal loads and write-through
+    // stores leave their lines there as plain ones do (profiles/serpentine_probe.txt), so the load
+    // and store policies are the same at both ends of a walk as in its middle.  (C3 37.37 -> 36.62
+    // ms (two runs: -2.0 %, -1.7 %), at every size: C2 10.28 -> 10.21, C3/2 slab 18.95 -> 18.86,
+    // C3/8 slab 6.23 -> 6.16 ms (profiles/serpentine_ab*.json); every step reversed instead of
+    // every other one: 38.79 vs 38.78 ms, nothing)
+    BAND_SERP = 32,
+    // compile-time; also step 0 of the band's cycle (EPI_PREC_DC_ND).  No read of the diagonal table
+    // D.  The band step runs only with the tridiagonal BJ(8) factors of A's current diagonal blocks
+    // (bj_op() hands out tri for the operator's current values_epoch only; the launch site in
+    // vtk_gmres.cpp states the guard), so A = M + C with C the x +- 1 couplings and the v +- 1
+    // couplings that cross an 8-row block edge, and
+    //   w = M^-1 A p = p + M^-1 (C p):
+    // the row sum y = C p skips the diagonal and the in-block v +- 1 products (the in-block
+    // couplings still enter bj_trim_group as sub / sup, from the per-line constants), z = M^-1 y,
+    // w = p + z.  One 8-B stream per row fewer (load, SPF operand, L2PF row); w differs from the D
+    // form in its last bits only
+    BAND_ND = 64,
+};
+
 // Line-band DCGS2 step (k_band_step): update pass of step j + SpMV, tridiagonal
 // BJ(8) and dots of step j+1 in one sweep over x-lines of L rows (SELL-64 uniform width 5, coded
 // columns, fp64 values; across ranks through the ghost lines).  grid workgroups (<= X lines, <= GMAX), partials of step j+1 in
@@ -583,16 +629,15 @@ struct BandK {
     int left_blk;                // halo block (0 / 1) holding the left neighbour line
     int xord = 0;                // bit 0: the slab starts at global line 0, bit 1: ends at the last line
     const double *lsv;           // line-separable values (vtk_csr::d_lsv) or null: SELL values
-    int canon;                   // with lsv: canonical rows (vtk_csr::lsv_canon), no codes read;
-                                 // 2: the SpMV as straight-line code per line order
-    int opt = 0;                 // kernel variant bits (vtk::Tuning::band_opt; vtk_band.hip OPT)
+    bool canon;                  // with lsv: canonical rows (vtk_csr::lsv_canon), no codes read (VMODE 2)
+    int opt = 0;                 // BandOpt bits
 };
 hipError_t launch_band_step(const BandK &a, int grid, int wu, hipStream_t s);
 // geometry (k_band_step): a workgroup of BAND_T threads owns <= BAND_LP rows of a
 // line (one part; parts per line = band_parts), BAND_WPC workgroups per CU (LDS-bound)
 constexpr int BAND_LP = 400, BAND_T = 448, BAND_WPC = 2;
 constexpr int BAND_JV = 19;    // basis vectors staged per line (j + 1 <= 19: restart <= 20)
-// band steps j <= BAND_J3 run three workgroups per CU (Tuning::band_opt bit 1): their LDS (ring +
+// band steps j <= BAND_J3 run three workgroups per CU (BAND_WPC3): their LDS (ring +
 // (j + 1) staged basis rows of BAND_LP doubles) fits three times into 160 KB, and their registers
 // the 80-VGPR cap (j = 3 / 4 fit too since the x update is inline, but measured within noise)
 constexpr int BAND_J3 = 2;

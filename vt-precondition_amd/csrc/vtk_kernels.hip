@@ -71,7 +71,7 @@ struct SpmvK {
 };
 
 // value of entry (row, c) from the line-separable tables; drow = D[row], (xl, v) the row's line
-// and position (vtk_band.hip k_lsv_build)
+// and position (vtk_ring.hip k_lsv_build)
 template <typename VT, bool HALO>
 __device__ __forceinline__ double lsv_value(const SpmvK<VT, HALO> &a, int row, int c, double drow, int xl, int v) {
     const int off = c - row, L = a.lsv_L, X = a.n_local / L;
