@@ -15,6 +15,8 @@
  *                          couplings (line-implicit x-direction solve)
  *   vtk_lineproduct_*   <- LinearOperator(matvec=lambda r: lu2.solve(D * lu1.solve(r))),
  *                          lu_i = splu(M_i): two line directions
+ *   vtk_linecyclic_*    <- LinearOperator(matvec=splu(M).solve), M = diagonal + the periodic
+ *                          lines' couplings, wrap included
  *   vtk_gmres          <- scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=, restart=,
  *                          maxiter=, M=) (scipy/sparse/linalg/_isolve/iterative.py:582-841)
  * The config/entry layer the reference does have (XML node lookups, ini_info.py:72-118;
@@ -176,7 +178,7 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * nowhere else (fail_step is a test hook: this rank fails its DCGS2 step of that index in the
  * first cycle, vtk_gmres).  Keys: band, band_lsv, sell_canon, band_canon, band_opt, band_long_rows, lsv_ring,
  * prof_perj, comm_solo, auto_band, grid4, c4_fused, g4_ring, g4_gr, g4_fast, line_fuse, cyc_ring,
- * line2_dc, bcg_fuse, fail_step.
+ * line2_dc, bcg_fuse, linec_serial, fail_step.
  * VTK_ERR_ARG for an unknown key; a VTK_<KEY> variable of a key removed in round 5 draws a
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
  * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
@@ -324,7 +326,7 @@ void vtk_prec_destroy(vtk_prec *M);
  * (4D); seg dividing Nx / world makes M independent of the rank count.  VTK_ERR_SINGULAR
  * when a pivot is zero or not finite.  Apply with vtk_prec_apply (or vtk_bjacobi_apply); use
  * as vtk_gmres's M. */
-typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1, VTK_PREC_LINE2 = 2 } vtk_prec_kind;
+typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1, VTK_PREC_LINE2 = 2, VTK_PREC_LINEC = 3 } vtk_prec_kind;
 int vtk_linejacobi_create(vtk_csr *A, int64_t stride, int64_t seg, vtk_prec **out);
 /* export the factors l | m | g (3 * n_local doubles; the oracle's orc_line_setup layout) */
 int vtk_linejacobi_factors(vtk_prec *M, double *f, int ptr_kind);
@@ -353,6 +355,35 @@ int vtk_lineproduct_create(vtk_csr *A, int64_t stride1, int64_t seg1, int64_t st
                            vtk_prec **out);
 /* which 0 / 1: the factors l | m | g of that direction (3 * n_local doubles); 2: D (n_local) */
 int vtk_lineproduct_factors(vtk_prec *M, int which, double *f, int ptr_kind);
+/* ---- periodic whole lines: cyclic x-line solves -----------------------------
+ * M keeps A's diagonal (per row the sum of its stored diagonal entries, in stored order) and every
+ * stored coupling between rows R and R' with R mod stride == R' mod stride, R / (stride period) ==
+ * R' / (stride period) and line indices (R / stride) mod period that differ by +-1 modulo period:
+ * each (block, R mod stride) is one cyclic tridiagonal system of `period` unknowns, the wrap
+ * coupling included.  SciPy statement: LinearOperator(matvec=splu(M).solve).  Vlasov operators:
+ * (stride, period) = (Nv, Nx) in 2D, (Ny Nvx Nvy, Nx) for the 4D x-lines, (Nvx Nvy, Ny) for the 4D
+ * y-lines.  `seg` is only the partition length of the solver, a recursive Schur complement on
+ * separators (segments of seg unknowns, one separator each; the separators' system is partitioned
+ * again until a level has at most `linec_serial` unknowns per line -- tuning key, default 64, read
+ * here -- which one lane per line solves).  It does not change M; the result is defined to
+ * rounding, not bit for bit.  No pivoting, at any level (as vtk_linejacobi_create).
+ * VTK_ERR_ARG unless period >= 3, seg >= 2, stride >= 1 and the rank's first row and row count are
+ * multiples of stride * period (every cyclic line on one rank: the 2D operators across ranks are
+ * refused).  VTK_ERR_SINGULAR when a pivot of any level is zero or not finite; the message names
+ * the row.  Apply, refresh (every level refactored; M invalid after a failed one) and destroy
+ * through vtk_prec_apply / vtk_prec_refresh / vtk_prec_destroy; usable as vtk_gmres's and
+ * vtk_bicgstab's M and in vtk_precond_matvec.  The vtk_linejacobi_* and vtk_lineproduct_* calls
+ * refuse it (VTK_ERR_STATE).  (additive, ABI 6) */
+int vtk_linecyclic_create(vtk_csr *A, int64_t stride, int64_t period, int64_t seg, vtk_prec **out);
+/* the partition: levels (the last one is the serial level), unknowns per line and level, whether
+ * the spikes are kept as one table per line (compact; 0: stored per row) */
+typedef struct {
+    int32_t levels;
+    int32_t compact;
+    int64_t stride, period, seg;
+    int64_t unknowns[32];
+} vtk_linec_info;
+int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out);
 /* z = M^-1 r for any preconditioner; *kind = vtk_prec_kind */
 int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int ptr_kind);
 int vtk_prec_kind_of(vtk_prec *M, int *kind);

@@ -25,7 +25,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {"prof_perj", &Tuning::prof_perj}, {"comm_solo", &Tuning::comm_solo}, {"auto_band", &Tuning::auto_band},
     {"grid4", &Tuning::grid4}, {"c4_fused", &Tuning::c4_fused}, {"g4_ring", &Tuning::g4_ring},
     {"g4_gr", &Tuning::g4_gr}, {"g4_fast", &Tuning::g4_fast}, {"line_fuse", &Tuning::line_fuse}, {"cyc_ring", &Tuning::cyc_ring},
-    {"line2_dc", &Tuning::line2_dc},
+    {"line2_dc", &Tuning::line2_dc}, {"linec_serial", &Tuning::linec_serial},
     {"bcg_fuse", &Tuning::bcg_fuse},
     {"fail_step", &Tuning::fail_step},
 };
@@ -539,6 +539,36 @@ int vtk_lineproduct_create(vtk_csr *A, int64_t stride1, int64_t seg1, int64_t st
     });
 }
 
+int vtk_linecyclic_create(vtk_csr *A, int64_t stride, int64_t period, int64_t seg, vtk_prec **out) {
+    if (!A || !out) return VTK_ERR_ARG;
+    vtk_ctx *c = A->ctx;
+    *out = nullptr;
+    if (stride < 1 || period < 3 || seg < 2)
+        return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create: stride must be >= 1, period >= 3 and seg >= 2");
+    if (stride > INT64_MAX / period || A->row_begin % (stride * period) != 0 || A->n_local % (stride * period) != 0)
+        return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create: the rank's first row and row count must be multiples of stride * "
+                                    "period (every cyclic line on one rank)");
+    return make_prec(A, VTK_PREC_LINEC, 0, out, [&](vtk_prec *M) -> int {
+        TRY(linec_plan(M, stride, period, seg));
+        return linec_factor(M);
+    });
+}
+
+int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out) {
+    if (!M || !out) return VTK_ERR_ARG;
+    if (M->kind != VTK_PREC_LINEC) return fail(M->A->ctx, VTK_ERR_STATE, "vtk_linecyclic_info: not a cyclic-line preconditioner");
+    const LineC &C = M->linec;
+    vtk_linec_info o{};
+    o.levels = C.nlev;
+    o.compact = 0;   // the spikes are stored per row
+    o.stride = C.stride;
+    o.period = C.period;
+    o.seg = C.seg;
+    for (int k = 0; k < C.nlev && k < 32; ++k) o.unknowns[k] = C.lev[k].period;
+    *out = o;
+    return VTK_OK;
+}
+
 int vtk_lineproduct_factors(vtk_prec *M, int which, double *f, int kind) {
     if (!M || !f) return VTK_ERR_ARG;
     vtk_ctx *c = M->A->ctx;
@@ -636,7 +666,7 @@ int vtk_prec_refresh(vtk_prec *M, int64_t *epoch) {
     HIPCHK(c, hipSetDevice(c->device));
     // the factors are overwritten from the first launch on: M is invalid until they are whole again
     const int64_t e = A->values_epoch;
-    const int rc = M->kind == VTK_PREC_LINE2 ? line2_factor(M) : M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
+    const int rc = M->kind == VTK_PREC_LINEC ? linec_factor(M) : M->kind == VTK_PREC_LINE2 ? line2_factor(M) : M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
     if (rc == VTK_ERR_SINGULAR) M->valid = false;
     if (rc != VTK_OK) return rc;
     M->valid = true;
@@ -740,6 +770,7 @@ void vtk_prec_destroy(vtk_prec *M) {
     (void)hipFree(M->line2.f);
     (void)hipFree(M->line2.ac);
     (void)hipFree(M->d_diag);
+    linec_free(M->linec);
     free_tiles(M->tiles);
     free_tiles(M->tiles_in);
     free_tiles(M->tiles_bd);

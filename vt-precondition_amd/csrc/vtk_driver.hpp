@@ -124,6 +124,10 @@ inline void prof_flush(vtk_ctx *c, int last_col = 1 << 30) {
 inline BjOp bj_op(const vtk_prec *M) {
     BjOp o;
     if (!M) return o;
+    if (M->kind == VTK_PREC_LINEC) {   // periodic whole lines: the three phases (launch_bj_apply)
+        o.linec = &M->linec;
+        return o;
+    }
     if (M->kind == VTK_PREC_LINE || M->kind == VTK_PREC_LINE2) {
         o.line = &M->line;
         if (M->kind == VTK_PREC_LINE2) {   // the product: both sweeps (launch_bj_apply)
@@ -154,6 +158,7 @@ inline bool bj8_tri(const vtk_prec *M) {
 
 // profile class of a standalone preconditioner apply
 inline const char *prec_cls(const vtk_prec *M) {
+    if (M && M->kind == VTK_PREC_LINEC) return "linec_apply";   // the three phases of the cyclic lines
     if (M && M->kind == VTK_PREC_LINE2) return "line2_apply";   // both sweeps of the product
     return M && M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply";
 }
@@ -161,10 +166,27 @@ inline const char *prec_cls(const vtk_prec *M) {
 // bytes per row of one direction's factors as a sweep reads them: m (compact) or l, m, g
 inline double line_row_bytes(const LineOp &L) { return L.compact ? 8.0 : 24.0; }
 
+// periodic whole lines, algorithmic bytes of the three phases: the level-0 sweep
+// reads r, l, m, g and writes y; the reduced part gathers per separator (r_s, a_s, c_s, two y read,
+// one value written) and runs every reduced level in place (sweep 40 B, correction 32 B per unknown,
+// its own gather; the last level's one lane per line reads its five factor rows); the level-0
+// correction reads y, V, W and the separator values and writes z
+inline double linec_sweep_bytes(const LineC &C) { return 40.0 * (double)C.n; }
+inline double linec_reduced_bytes(const LineC &C) {
+    double b = C.nlev > 1 ? 48.0 * (double)C.lev[1].n : 0.0;
+    for (int k = 1; k < C.nlev; ++k) b += (k + 1 < C.nlev ? 72.0 + 48.0 * (double)C.lev[k + 1].n / (double)std::max<int64_t>(C.lev[k].n, 1) : 88.0) * (double)C.lev[k].n;
+    return b;
+}
+inline double linec_correct_bytes(const LineC &C) { return 32.0 * (double)C.n + (C.nlev > 1 ? 8.0 * (double)C.lev[1].n : 0.0); }
+
 // algorithmic bytes per row of one BJ application (tridiagonal: the SELL kernels read only m)
 inline double bj_row_bytes(const vtk_prec *M) {
     if (!M) return 0.0;
     if (M->kind == VTK_PREC_LINE) return line_row_bytes(M->line);
+    // the cyclic lines: the three phases' bytes less the r read and z written that the callers add
+    if (M->kind == VTK_PREC_LINEC)
+        return (linec_sweep_bytes(M->linec) + linec_reduced_bytes(M->linec) + linec_correct_bytes(M->linec)) /
+                   (double)std::max<int64_t>(M->linec.n, 1) - 16.0;
     // the product: both directions' factors, D, and t = M1^-1 r written and read back
     if (M->kind == VTK_PREC_LINE2) return line_row_bytes(M->line) + line_row_bytes(M->line2) + 8.0 + 16.0;
     if (bj_op(M).tri) return M->A->use_sell ? 8.0 : 24.0;
@@ -424,6 +446,9 @@ int update_finish(vtk_csr *A, UpdateScratch &u);
 int bj_factor(vtk_prec *M);
 int line_factor(vtk_prec *M);
 int line2_factor(vtk_prec *M);
+int linec_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);
+int linec_factor(vtk_prec *M);
+void linec_free(LineC &C);
 int prec_usable(const vtk_prec *M, const char *who);
 
 // ---- vtk_gmres.cpp / vtk_bicg.cpp: the drivers, and the step launches vtk_precond_matvec shares -

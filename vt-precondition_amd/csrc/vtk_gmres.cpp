@@ -104,7 +104,7 @@ struct StepPlan {
     bool g4_fits, g4_fused, g4_ring, wide9, ring4, fused;
     bool ring0;      // step 0 of a band cycle through the x-line ring
     bool split;      // interior / boundary pieces of the fused step (world > 1)
-    bool line_dc, line2_step, line_lsv, line_canon, line_fuse;
+    bool line_dc, line2_step, linec_step, line_lsv, line_canon, line_fuse;
     bool band_lsv, band_canon, band_nd;
     int band_opt;
     bool resid_fused, resid_g4, resid_ring;   // the cycle-end residual's kernel (residual())
@@ -141,8 +141,10 @@ StepPlan step_plan(const Solver &s) {
     P.line_dc = M && M->kind == VTK_PREC_LINE && M->line.seg >= 1 && M->line.seg <= 32 && s.G <= GMAX;
     // line product: SpMV, sweep 1 in place, sweep 2 with the dots (tuning line2_dc)
     P.line2_step = M && M->kind == VTK_PREC_LINE2 && M->line2.seg >= 1 && M->line2.seg <= 32 && s.G <= GMAX;
+    // periodic whole lines: SpMV, the three apply phases, then the dots kernel
+    P.linec_step = M && M->kind == VTK_PREC_LINEC && s.G <= GMAX;
     // line path on a line-separable operator: the SpMV from the tables (VTK_BAND_LSV=0: SELL)
-    P.line_lsv = (P.line_dc || P.line2_step) && line_lsv_ok(c, A);
+    P.line_lsv = (P.line_dc || P.line2_step || P.linec_step) && line_lsv_ok(c, A);
     P.ft = M ? &M->tiles : &A->tiles;
     P.b_csr = matrix_bytes(A);
     P.b_lsv = P.b_csr - 8.0 * (double)A->sell.entries + 8.0 * (double)n;
@@ -299,7 +301,15 @@ int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
         Prof pf(c, "spmv", j, P.b_csr + 2 * n8);
         SOFT(launch_spmv(spmv_in(A, &A->tiles, pj), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, stop, j, c->stream));
     }
-    if (P.line2_step) {
+    if (P.linec_step) {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
+        const LineC &lc = s.M->linec;
+        { Prof pf(c, "linec_sweep", j, linec_sweep_bytes(lc));
+          SOFT(launch_linec_phase(lc, 0, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
+        { Prof pf(c, "linec_reduced", j, linec_reduced_bytes(lc));
+          SOFT(launch_linec_phase(lc, 1, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
+        { Prof pf(c, "linec_correct", j, linec_correct_bytes(lc));
+          SOFT(launch_linec_phase(lc, 2, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
+    } else if (P.line2_step) {
         const LineOp &l2 = s.M->line2;
         { Prof pf(c, "line_apply", j, line_row_bytes(lo) * n + 2 * n8);   // t = M1^-1 y in place on the SpMV's output
           SOFT(launch_line_apply(lo, s.tmp, s.tmp, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
@@ -352,7 +362,7 @@ int operator_step(Solver &s, const StepPlan &P, int j, double *pj, int &cnt) {
     if (P.ring0 && j == 0) return step_ring_start(s, P, j, pj, b_step, cnt);
     if (P.fused && P.split) return step_fused_split(s, j, pj, b_step, cnt);
     if (P.fused) return step_fused(s, P, j, pj, b_step, cnt);
-    if (P.line_dc || P.line2_step) return step_line(s, P, j, pj, cnt);
+    if (P.line_dc || P.line2_step || P.linec_step) return step_line(s, P, j, pj, cnt);
     if (P.ring4) return step_g4_ring(s, P, j, pj, cnt);
     Red h0, d0;
     return precond_matvec(s, P, pj, s.w, j, h0, d0, false);

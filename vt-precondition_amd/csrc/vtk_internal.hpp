@@ -145,6 +145,24 @@ struct LineOp {
     int compact = 0;
 };
 
+// periodic whole-line operator (vtk_linecyclic_create; vtk_linec.hip): every
+// (block, j = R mod stride) of the rank's rows is one cyclic tridiagonal system of `period`
+// unknowns, element i of it at local index (block period + i) stride + j.  Level 0 is the lines
+// themselves, level k + 1 the separators (one per segment) of level k, in the same layout with
+// period = level k's segments per line; the last level has one segment per line.
+constexpr int LINEC_MAXLEV = 32;
+struct LineCLevel {
+    double *f = nullptr;   // l | m | g | V | W (n doubles each): Thomas factors and spikes
+    double *x = nullptr;   // levels >= 1: the level's right-hand side, solved in place (n doubles)
+    int64_t n = 0, period = 0, seg = 0, nseg = 0;   // unknowns, per line: unknowns, segment length, segments
+};
+struct LineC {
+    int64_t n = 0, row0 = 0, stride = 1, period = 0, seg = 0, nblk = 0;
+    int nlev = 0, serial = 64;
+    LineCLevel lev[LINEC_MAXLEV];
+    double *minv = nullptr;   // [nblk stride] the last level's reciprocal pivots
+};
+
 // 4D phase-space grid of the Vlasov operators (row = ((ix Ny + iy) Nvx + jvx) Nvy + jvy, x and y
 // periodic, vx and vy Dirichlet): every row couples to x +- 1 (value by jvx),
 // y +- 1 (by jvy), vx +- 1 (by ix), vy +- 1 (by iy) and itself, in ascending column order.  When
@@ -226,6 +244,8 @@ struct Tuning {
                               // (k_lsv_ring_epi, ~that many workgroups; 2D line-separable rows)
     int bcg_fuse = 1;         // BiCGStab with BJ, bs in {1, 2, 4, 8}: phat = M p and shat = M s inside
                               // k_bcg_p / k_bcg_s (0: the separate apply; the same bits either way)
+    int linec_serial = 64;    // line_cyclic: a reduced level of at most this many unknowns per line is the
+                              // last, solved by one lane per line (read at vtk_linecyclic_create)
     int fail_step = -1;       // (test hook) >= 0: this rank's DCGS2 step of that index fails in the
                               // first cycle as a refused launch would (the peer-failure vote, vtk_gmres);
                               // vtk_bicgstab: the first launch of that loop index is refused
@@ -357,6 +377,8 @@ struct vtk_prec {
     vtk::LineOp line2;
     bool line2_compact_ok = false;
     double *d_diag = nullptr;
+    // periodic whole lines (vtk_linecyclic_create): kind VTK_PREC_LINEC
+    vtk::LineC linec;
     // vtk_prec_refresh: what creation was asked for, and the operator values the
     // factors were computed from
     int setup = VTK_BJ_SETUP_EXACT;  // resolved vtk_bj_setup (EXACT or MFMA)
@@ -403,6 +425,7 @@ struct BjOp {
     // M2 = line2 and D = diag (A's diagonal, n doubles)
     const LineOp *line2 = nullptr;
     const double *diag = nullptr;
+    const LineC *linec = nullptr;   // periodic whole lines instead (vtk_linecyclic_create)
 };
 
 // mm[0] = min, mm[1] = max of idx[0..n) (mm preset to INT_MAX, INT_MIN)
@@ -464,6 +487,19 @@ hipError_t launch_line2_apply(const LineOp &L, const double *D, const double *t,
                               double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, double *w, const double *V, int64_t ld,
                            int j, const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s);
+// periodic whole lines (vtk_linec.hip).  launch_linec_setup: level lev's factors and spikes (level
+// 0 from the CSR, else from co = a | b | c), then its separators' system into co (the next level's
+// coefficients) or, at the last level, C.minv; bad[lev] / bad[nlev]: the smallest element index of
+// that level / of the last level's pivots that is zero or not finite (preset ~0).
+// launch_linec_phase: 0 the level-0 sweep (y into z's interior rows), 1 the separators' right-hand
+// sides and every reduced level, 2 the level-0 correction with part0 = sum z^2, part1 = sum v0 z
+// over grid workgroups.  r and z may alias.  launch_linec_apply: the three in order
+hipError_t launch_linec_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
+                              const LineC &C, int lev, double *co, unsigned long long *bad, hipStream_t s);
+hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double *z, const double *v0, double *part0,
+                              double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+hipError_t launch_linec_apply(const LineC &C, const double *r, double *z, const double *v0, double *part0,
+                              double *part1, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_bj_tri_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
                                int64_t n, int bs, const double *inv, double *tri, int64_t ld, int *flags,
                                hipStream_t s);

@@ -1,5 +1,5 @@
 // vtk_precond.cpp -- preconditioner factors from the operator's current values: block Jacobi, line
-// Jacobi, the two-direction line product (vtk_*_create and vtk_prec_refresh call these).
+// Jacobi, the two-direction line product, the periodic whole lines (vtk_*_create and vtk_prec_refresh call these).
 #include <climits>
 
 #include "vtk_driver.hpp"
@@ -141,6 +141,95 @@ int line2_factor(vtk_prec *M) {
     const unsigned long long br = std::min(br1, br2);
     if (br != ~0ull)
         return fail(c, VTK_ERR_SINGULAR, "vtk_lineproduct_create: zero or non-finite line pivot at row " + std::to_string(br));
+    return VTK_OK;
+}
+
+// ---- periodic whole lines (vtk_linecyclic_create; vtk_linec.hip) ----------------
+void linec_free(LineC &C) {
+    for (int k = 0; k < LINEC_MAXLEV; ++k) {
+        (void)hipFree(C.lev[k].f);
+        (void)hipFree(C.lev[k].x);
+        C.lev[k] = LineCLevel{};
+    }
+    (void)hipFree(C.minv);
+    C.minv = nullptr;
+    C.nlev = 0;
+}
+
+// The levels of M->linec and their storage (the arguments are checked by the caller).  Level 0 cuts
+// the lines into segments of seg; a level of the separators is cut again while it has more than
+// linec_serial unknowns per line and more than one segment; the last level is one segment per line.
+int linec_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    LineC &C = M->linec;
+    C.n = A->n_local;
+    C.row0 = A->row_begin;
+    C.stride = stride;
+    C.period = period;
+    C.seg = seg;
+    C.nblk = A->n_local / (stride * period);
+    C.serial = std::max(1, c->tune.linec_serial);
+    const int64_t lines = C.nblk * stride;
+    int64_t P = period;
+    for (int k = 0;; ++k) {
+        if (k >= LINEC_MAXLEV) return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create: too many levels");
+        LineCLevel &v = C.lev[k];
+        const bool last = k > 0 && (P <= C.serial || P <= seg);
+        v.period = P;
+        v.seg = last ? P : std::min(seg, P);
+        v.nseg = (P + v.seg - 1) / v.seg;
+        v.n = lines * P;
+        HIPCHK(c, hipMalloc(&v.f, 5 * (size_t)std::max<int64_t>(v.n, 1) * sizeof(double)));
+        if (k > 0) HIPCHK(c, hipMalloc(&v.x, (size_t)std::max<int64_t>(v.n, 1) * sizeof(double)));
+        C.nlev = k + 1;
+        if (last) break;
+        P = v.nseg;
+    }
+    HIPCHK(c, hipMalloc(&C.minv, (size_t)std::max<int64_t>(lines, 1) * sizeof(double)));
+    return VTK_OK;
+}
+
+// global row of element idx of level lev: a level's element i is the separator of segment i of the
+// level below
+static int64_t linec_row(const LineC &C, int lev, int64_t idx) {
+    const int64_t j = idx % C.stride, t = idx / C.stride;
+    int64_t i = t % C.lev[lev].period;
+    const int64_t blk = t / C.lev[lev].period;
+    for (int k = lev; k > 0; --k) i = std::min((i + 1) * C.lev[k - 1].seg, C.lev[k - 1].period) - 1;
+    return C.row0 + (blk * C.period + i) * C.stride + j;
+}
+
+// Every level's factors and spikes, top down, from the operator's current values (creation and
+// vtk_prec_refresh).  VTK_ERR_SINGULAR: a zero or non-finite pivot at some level (the first such
+// level's smallest row is named).
+int linec_factor(vtk_prec *M) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    const LineC &C = M->linec;
+    if (C.n <= 0) return VTK_OK;
+    DBuf bad, co;
+    std::vector<unsigned long long> hb((size_t)C.nlev + 1, ~0ull);
+    TRY(dalloc(c, bad, hb.size() * sizeof(unsigned long long)));
+    TRY(dalloc(c, co, 3 * (size_t)std::max<int64_t>(C.lev[1].n, 1) * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(bad.p, hb.data(), hb.size() * 8, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < C.nlev; ++k) {
+        Prof pf(c, "linec_setup", -1, (k == 0 ? matrix_bytes(A) : 24.0 * (double)C.lev[k].n) + 72.0 * (double)C.lev[k].n);
+        HIPCHK(c, launch_linec_setup(A->d_indptr, A->d_indices, A->d_data, A->fp32, C, k, co.as<double>(),
+                                     bad.as<unsigned long long>(), c->stream));
+    }
+    if (c->prof_on) prof_flush(c);
+    HIPCHK(c, hipMemcpyAsync(hb.data(), bad.p, hb.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k <= C.nlev; ++k) {
+        if (hb[k] == ~0ull) continue;
+        // the last level's pivot belongs to its separator, the line's last unknown
+        const int lev = std::min(k, C.nlev - 1);
+        const int64_t idx = k < C.nlev ? (int64_t)hb[k]
+                                       : ((int64_t)hb[k] / C.stride * C.lev[lev].period + C.lev[lev].period - 1) * C.stride + (int64_t)hb[k] % C.stride;
+        return fail(c, VTK_ERR_SINGULAR, "vtk_linecyclic_create: zero or non-finite pivot at row " + std::to_string(linec_row(C, lev, idx)) +
+                                             " (level " + std::to_string(lev) + ")");
+    }
     return VTK_OK;
 }
 

@@ -29,7 +29,8 @@ from ._abi import check, lib
 
 __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "vlasov_operator", "block_jacobi",
            "gmres", "VlasovParams", "vlasov_params", "rhs_splitmix", "partition_rows",
-           "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi", "line_product", "LineProduct",
+           "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi", "line_product", "LineProduct", "line_cyclic", "LineCyclic",
+           "vlasov_line_period",
            "vlasov_line_directions",
            "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats",
            "ArnoldiCapture", "last_arnoldi"]
@@ -753,6 +754,12 @@ def vlasov_line_stride(params) -> int:
     return sh[1] * sh[2] * sh[3]
 
 
+def vlasov_line_period(params) -> int:
+    """Unknowns of one periodic x-line of a Vlasov operator, Nx: :func:`line_cyclic`'s ``period``
+    next to :func:`vlasov_line_stride`'s stride.  (The 4D y-lines: stride Nvx*Nvy, period Ny.)"""
+    return int(params.shape[0])
+
+
 def vlasov_line_directions(params) -> list[int]:
     """The line strides of a Vlasov operator, strongest advection direction first: [1] (1D),
     [Nv, 1] (2D: x, then v), [Ny*Nvx*Nvy, Nvx*Nvy] (4D: x, then y).  The first entry is
@@ -827,8 +834,66 @@ def line_product(A: CsrOperator, dir1, dir2) -> LineProduct:
     return LineProduct(A, dir1, dir2)
 
 
-_PRECS = (BlockJacobi, LineJacobi, LineProduct)
-_PRECS_TEXT = "None, vtkrylov.BlockJacobi, vtkrylov.LineJacobi or vtkrylov.LineProduct"
+class LineCyclic:
+    """Periodic whole-line preconditioner: M = A's diagonal + every coupling
+    between rows of one line -- R mod ``stride`` and R // (``stride`` * ``period``) equal -- whose
+    line indices (R // stride) mod period differ by +-1 modulo ``period``, the wrap included: one
+    cyclic tridiagonal system of ``period`` unknowns per line.  SciPy statement:
+    ``LinearOperator(matvec=splu(M).solve)``.  ``vtk_linecyclic_create``.
+
+    ``seg`` is only the partition length of the solver (a recursive Schur complement on
+    separators); it does not change M.  Vlasov operators: ``stride`` from
+    :func:`vlasov_line_stride`, ``period`` from :func:`vlasov_line_period`.  Every cyclic line
+    must lie on one rank (ValueError otherwise)."""
+
+    def __init__(self, A: CsrOperator, stride: int, period: int, seg: int = 25):
+        h = C.c_void_p()
+        check(lib().vtk_linecyclic_create(A.handle, int(stride), int(period), int(seg), C.byref(h)), A.ctx.handle)
+        self._h = h
+        self.A = A
+        self.stride = int(stride)
+        self.period = int(period)
+        self.seg = int(seg)
+        self.shape = A.shape
+        self.dtype = np.dtype(np.float64)
+        self._epoch = A.values_epoch
+
+    def refresh(self):
+        """Refactor every level from the operator's current values (``vtk_prec_refresh``).
+        LinAlgError on a zero pivot at any level -- unusable (VtkError, status ERR_STATE) until a
+        later refresh succeeds."""
+        return _refresh(self)
+
+    @property
+    def values_epoch(self) -> int:
+        """``A.values_epoch`` of the values the factors were computed from."""
+        return self._epoch
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """``levels`` (the last one is solved by one lane per line), ``unknowns`` per line and
+        level, ``compact`` (spikes kept as one table per line; False: stored per row)."""
+        o = _abi.LinecInfo()
+        check(lib().vtk_linecyclic_info(self._h, C.byref(o)), self.A.ctx.handle)
+        return {"levels": int(o.levels), "unknowns": [int(o.unknowns[k]) for k in range(o.levels)],
+                "compact": bool(o.compact), "stride": int(o.stride), "period": int(o.period), "seg": int(o.seg)}
+
+    matvec = LineJacobi.matvec
+    __matmul__ = LineJacobi.__matmul__
+    close = LineJacobi.close
+    __del__ = LineJacobi.__del__
+
+
+def line_cyclic(A: CsrOperator, stride: int, period: int, seg: int = 25) -> LineCyclic:
+    """``line_cyclic(A, stride, period, seg=25)``: see :class:`LineCyclic`."""
+    return LineCyclic(A, stride, period, seg)
+
+
+_PRECS = (BlockJacobi, LineJacobi, LineProduct, LineCyclic)
+_PRECS_TEXT = "None, vtkrylov.BlockJacobi, vtkrylov.LineJacobi, vtkrylov.LineProduct or vtkrylov.LineCyclic"
 
 
 @dataclass

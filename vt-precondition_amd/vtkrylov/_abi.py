@@ -115,6 +115,8 @@ PROTOTYPES = {
     "vtk_linejacobi_factors": (C.c_int, [P, P, C.c_int]),
     "vtk_lineproduct_create": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(P)]),
     "vtk_lineproduct_factors": (C.c_int, [P, C.c_int, P, C.c_int]),
+    "vtk_linecyclic_create": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(P)]),
+    "vtk_linecyclic_info": (C.c_int, [P, C.c_void_p]),
     "vtk_prec_apply": (C.c_int, [P, P, P, C.c_int]),
     "vtk_linejacobi_set_compact": (C.c_int, [P, C.c_int]),
     "vtk_linejacobi_get_compact": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -156,6 +158,11 @@ class BandGeometry(C.Structure):
 class LayoutInfo(C.Structure):
     _fields_ = [("layout", C.c_int), ("matrix_bytes", C.c_double), ("sell_chunks", C.c_int64),
                 ("sell_entries", C.c_int64), ("wide_chunks", C.c_int64)]
+
+
+class LinecInfo(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("compact", C.c_int32), ("stride", C.c_int64), ("period", C.c_int64),
+                ("seg", C.c_int64), ("unknowns", C.c_int64 * 32)]
 
 
 class KernelProfile(C.Structure):

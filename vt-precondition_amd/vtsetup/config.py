@@ -80,6 +80,9 @@ class SolverConfig:
     # entry of vtkrylov.vlasov_line_directions, and line_segment)
     line_stride2: int = 0
     line_segment2: int = 0
+    # preconditioner type line_cyclic: the unknowns of one periodic line (optional node; 0 = absent:
+    # vtkrylov.vlasov_line_period, Nx)
+    line_period: int = 0
 
     @classmethod
     def load(cls, path: str = DEFAULT_XML, **overrides) -> "SolverConfig":
@@ -111,10 +114,11 @@ class SolverConfig:
         cfg.method = (t.get_optional("solver/method", "gmres") or "gmres").lower()
         cfg.line_stride2 = int(t.get_optional("preconditioner/line_stride2", "0") or 0)
         cfg.line_segment2 = int(t.get_optional("preconditioner/line_segment2", "0") or 0)
+        cfg.line_period = int(t.get_optional("preconditioner/line_period", "0") or 0)
         for k, v in overrides.items():
             if v is not None:
                 setattr(cfg, k, v)
-        if cfg.preconditioner not in ("block_jacobi", "line_jacobi", "line_product", "none"):
+        if cfg.preconditioner not in ("block_jacobi", "line_jacobi", "line_product", "line_cyclic", "none"):
             raise ValueError(f"unknown preconditioner {cfg.preconditioner!r}")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")

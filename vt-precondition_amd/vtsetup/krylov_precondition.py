@@ -109,6 +109,23 @@ class KrylovPrecondition:
             seg2 = c.line_segment2 if c.line_segment2 > 0 else c.line_segment
             self.M = vk.line_product(self.A, (stride, c.line_segment), (stride2, seg2))
             info.update(line_stride=stride, line_segment=c.line_segment, line_stride2=stride2, line_segment2=seg2)
+        elif c.preconditioner == "line_cyclic":
+            # periodic whole x-lines (vtkrylov.line_cyclic): stride as for line_jacobi, the period Nx
+            # unless preconditioner/line_period names it; line_segment is the solver's partition length
+            stride, period = c.line_stride, c.line_period
+            if not c.operator_file:
+                prm = vk.vlasov_params(c.dim, c.shape)
+                stride = stride if stride > 0 else vk.vlasov_line_stride(prm)
+                period = period if period > 0 else vk.vlasov_line_period(prm)
+            elif stride <= 0:
+                stride = self.A.line_band
+            if stride > 0 and period <= 0 and c.operator_file and self.A.n_global % stride == 0:
+                period = self.A.n_global // stride   # a 2D operator file: every line spans the grid
+            if stride <= 0 or period <= 0:
+                raise ValueError("line_cyclic needs preconditioner/line_stride and preconditioner/line_period "
+                                 "(an operator file without a detected x-line structure has neither)")
+            self.M = vk.line_cyclic(self.A, stride, period, c.line_segment)
+            info.update(line_stride=stride, line_period=period, line_segment=c.line_segment)
         info["t_setup_s"] = self._max(time.perf_counter() - t)
         self.result["preconditioner"] = info
 
@@ -271,7 +288,7 @@ def test_main(argv=None) -> int:
     ap.add_argument("--config")
     ap.add_argument("--report")
     ap.add_argument("--operator-file", help="SciPy save_npz CSR archive to solve")
-    ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "line_product", "none"])
+    ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "line_product", "line_cyclic", "none"])
     ap.add_argument("--orth", choices=["auto", "mgs", "dcgs2"])
     ap.add_argument("--method", choices=["gmres", "bicgstab"], help="solver (overrides solver/method)")
     ap.add_argument("--gpus", type=int, help="ranks (overrides run/gpus)")
