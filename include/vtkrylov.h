@@ -17,6 +17,9 @@
  *                          lu_i = splu(M_i): two line directions
  *   vtk_linecyclic_*    <- LinearOperator(matvec=splu(M).solve), M = diagonal + the periodic
  *                          lines' couplings, wrap included
+ *   vtk_neumann_*       <- LinearOperator(matvec=mv), mv(r): z = M(r); degree - 1 times
+ *                          z = z + M(r - A @ z) -- the Neumann series of M^-1 A around any of the
+ *                          preconditioners above
  *   vtk_gmres          <- scipy.sparse.linalg.gmres(A, b, x0, rtol=, atol=, restart=,
  *                          maxiter=, M=) (scipy/sparse/linalg/_isolve/iterative.py:582-841)
  * The config/entry layer the reference does have (XML node lookups, ini_info.py:72-118;
@@ -178,7 +181,7 @@ int vtk_ctx_synchronize(vtk_ctx *ctx);
  * nowhere else (fail_step is a test hook: this rank fails its DCGS2 step of that index in the
  * first cycle, vtk_gmres).  Keys: band, band_lsv, sell_canon, band_canon, band_opt, band_long_rows, lsv_ring,
  * prof_perj, comm_solo, auto_band, grid4, c4_fused, g4_ring, g4_gr, g4_fast, line_fuse, cyc_ring,
- * line2_dc, bcg_fuse, linec_serial, fail_step.
+ * line2_dc, bcg_fuse, linec_serial, neu_fuse, neu_dc, fail_step.
  * VTK_ERR_ARG for an unknown key; a VTK_<KEY> variable of a key removed in round 5 draws a
  * warning on stderr at context creation and is otherwise ignored.  (ABI 5; fail_step ABI 6;
  * band_long_rows round 6: band_opt bits 3 and 4 only on ranks of at least that many rows;
@@ -326,7 +329,7 @@ void vtk_prec_destroy(vtk_prec *M);
  * (4D); seg dividing Nx / world makes M independent of the rank count.  VTK_ERR_SINGULAR
  * when a pivot is zero or not finite.  Apply with vtk_prec_apply (or vtk_bjacobi_apply); use
  * as vtk_gmres's M. */
-typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1, VTK_PREC_LINE2 = 2, VTK_PREC_LINEC = 3 } vtk_prec_kind;
+typedef enum { VTK_PREC_BJACOBI = 0, VTK_PREC_LINE = 1, VTK_PREC_LINE2 = 2, VTK_PREC_LINEC = 3, VTK_PREC_NEUMANN = 4 } vtk_prec_kind;
 int vtk_linejacobi_create(vtk_csr *A, int64_t stride, int64_t seg, vtk_prec **out);
 /* export the factors l | m | g (3 * n_local doubles; the oracle's orc_line_setup layout) */
 int vtk_linejacobi_factors(vtk_prec *M, double *f, int ptr_kind);
@@ -384,6 +387,49 @@ typedef struct {
     int64_t unknowns[32];
 } vtk_linec_info;
 int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out);
+/* ---- Neumann-series (polynomial) wrapper around any preconditioner above --------
+ * N_k^-1 r:  z_1 = M^-1 r;  z_{i+1} = z_i + M^-1 (r - A z_i), i = 1 .. k-1, with k = degree and
+ * M = M_base: the degree-(k-1) Neumann series of M^-1 A, equal to k steps of preconditioned
+ * Richardson from 0; N_k^-1 = (I - (I - M^-1 A)^k) A^-1.  More operator work per Krylov vector, so a
+ * solve needs fewer Krylov vectors.  SciPy statement:
+ *     def mv(r):
+ *         z = M(r)
+ *         for _ in range(degree - 1):
+ *             z = z + M(r - A @ z)
+ *         return z
+ *     LinearOperator((n, n), matvec=mv)
+ * The series helps only while the eigenvalues of M^-1 A stay inside the unit disc around 1: with
+ * block Jacobi on the Vlasov operators degree 2 halves the iterations and degree 3 stalls GMRES(20);
+ * the line product takes every degree (CPU table).  Nothing selects the wrapper by
+ * default.
+ * Bit-level definition (the library is compiled with -ffp-contract=off): t = r - (A z), the SpMV's
+ * row sum rounded to double, then one subtraction; u = M^-1 t, exactly the base's apply; z + u, one
+ * addition per row.  With block Jacobi (either apply mode), line Jacobi and the line product the
+ * result equals the composition of vtk_spmv and vtk_prec_apply with those two operations, bit for
+ * bit, whichever kernels run it (one fused launch per correction for block Jacobi with bs 1, 2, 4, 8
+ * on fused tiles -- tuning neu_fuse --, the addition inside the base's last sweep for the line kinds);
+ * with the periodic lines to rounding, as that base is defined.  degree = 1 is the base, bit for bit.
+ * 1 <= degree <= 8 (VTK_ERR_ARG).  The wrapper BORROWS its base: the base must outlive every use of
+ * the wrapper -- a use after the base's vtk_prec_destroy returns VTK_ERR_STATE -- and destroying the
+ * wrapper leaves the base alone.  VTK_ERR_ARG for a base that is itself a wrapper or was built on
+ * another operator.  vtk_prec_refresh on the wrapper refreshes the base (its errors pass through,
+ * VTK_ERR_SINGULAR with the base's row included); the wrapper's epoch is the base's, and a base
+ * refreshed or lagging on its own is seen by the wrapper at its next use.  Apply and destroy through
+ * vtk_prec_apply / vtk_prec_destroy; usable as vtk_gmres's and vtk_bicgstab's M and in
+ * vtk_precond_matvec, on one rank and across ranks (every correction exchanges its halo).  The
+ * line-band DCGS2 step is not taken with it.  The kind-specific vtk_bjacobi_*, vtk_linejacobi_*,
+ * vtk_lineproduct_* and vtk_linecyclic_* calls refuse it (VTK_ERR_STATE).  Device memory: three
+ * vectors of n_local doubles.  Tuning key neu_dc (default 1): in a DCGS2 step the last correction's
+ * addition also leaves the step's dots (line Jacobi and line product with segments <= 32, and the
+ * plain addition); 0: the dots kernel follows.  (additive, ABI 6) */
+int vtk_neumann_create(vtk_csr *A, vtk_prec *M_base, int degree, vtk_prec **out);
+typedef struct {
+    int32_t degree;
+    int32_t base_kind;   /* vtk_prec_kind of the base */
+    int32_t fused;       /* 1: each correction is one SpMV launch with the base in its epilogue */
+    int32_t base_alive;  /* 0: the base has been destroyed (every use returns VTK_ERR_STATE) */
+} vtk_neu_info;
+int vtk_neumann_info(vtk_prec *M, vtk_neu_info *out);
 /* z = M^-1 r for any preconditioner; *kind = vtk_prec_kind */
 int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int ptr_kind);
 int vtk_prec_kind_of(vtk_prec *M, int *kind);

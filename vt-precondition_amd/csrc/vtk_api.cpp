@@ -26,7 +26,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {"grid4", &Tuning::grid4}, {"c4_fused", &Tuning::c4_fused}, {"g4_ring", &Tuning::g4_ring},
     {"g4_gr", &Tuning::g4_gr}, {"g4_fast", &Tuning::g4_fast}, {"line_fuse", &Tuning::line_fuse}, {"cyc_ring", &Tuning::cyc_ring},
     {"line2_dc", &Tuning::line2_dc}, {"linec_serial", &Tuning::linec_serial},
-    {"bcg_fuse", &Tuning::bcg_fuse},
+    {"bcg_fuse", &Tuning::bcg_fuse}, {"neu_fuse", &Tuning::neu_fuse}, {"neu_dc", &Tuning::neu_dc},
     {"fail_step", &Tuning::fail_step},
 };
 // switches of earlier rounds whose alternative lost its A/B: an environment that
@@ -114,6 +114,7 @@ int make_prec(vtk_csr *A, int kind, int bs, vtk_prec **out, Fill fill) {
     vtk_ctx *c = A->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     auto *M = new vtk_prec();
+    prec_register(M);
     struct Guard { vtk_prec *&m; ~Guard() { if (m) vtk_prec_destroy(m); } } g{M};
     M->A = A;
     M->device = c->device;
@@ -607,6 +608,40 @@ int vtk_linejacobi_get_compact(vtk_prec *M, int *in_use, int *available) {
 
 int vtk_prec_apply(vtk_prec *M, const double *r, double *z, int kind) { return vtk_bjacobi_apply(M, r, z, kind); }
 
+int vtk_neumann_create(vtk_csr *A, vtk_prec *base, int degree, vtk_prec **out) {
+    vtk_ctx *c = A ? A->ctx : nullptr;
+    if (degree < 1 || degree > 8) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: degree must be in [1, 8]");
+    if (!A || !base || !out) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: NULL argument");
+    *out = nullptr;
+    if (!prec_alive(base, 0)) return fail(c, VTK_ERR_STATE, "vtk_neumann_create: the base preconditioner has been destroyed");
+    if (base->kind == VTK_PREC_NEUMANN) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: the base is itself a Neumann wrapper (no nesting)");
+    if (base->A != A) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: the base preconditioner was built for another operator");
+    TRY(prec_usable(base, "vtk_neumann_create"));
+    const int rc = make_prec(A, VTK_PREC_NEUMANN, 0, out, [&](vtk_prec *M) -> int {
+        M->base = base;
+        M->base_id = base->id;
+        M->degree = degree;
+        // z_i alternate between two vectors, t = r - A z_i in the third (64-row padding: 16-byte rows)
+        const int64_t ld = round_up(std::max<int64_t>(A->n_local, 1), 64);
+        if (degree > 1) HIPCHK(c, hipMalloc(&M->d_neu, 3 * (size_t)ld * sizeof(double)));
+        return VTK_OK;
+    });
+    if (rc == VTK_OK) (*out)->epoch = base->epoch;   // the wrapper's epoch is its base's
+    return rc;
+}
+
+int vtk_neumann_info(vtk_prec *M, vtk_neu_info *out) {
+    if (!M || !out) return VTK_ERR_ARG;
+    if (M->kind != VTK_PREC_NEUMANN) return fail(M->A->ctx, VTK_ERR_STATE, "vtk_neumann_info: not a Neumann wrapper");
+    vtk_neu_info o{};
+    o.degree = M->degree;
+    o.base_alive = prec_alive(M->base, M->base_id) ? 1 : 0;
+    o.base_kind = o.base_alive ? M->base->kind : -1;
+    o.fused = o.base_alive && M->degree > 1 && neu_fused(M) ? 1 : 0;
+    *out = o;
+    return VTK_OK;
+}
+
 // w = M^-1 A x through the launch the solver's split DCGS2 step uses for this operator (ADVICE r5:
 // the kernel-level pin of k_g4_ring against k_sell<EPI_PREC>): the 4D ring kernel when it applies
 // -- across ranks in the solver's form, interior groups while the halo planes travel, then the
@@ -652,8 +687,7 @@ int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int 
         TRY(dalloc(c, t, std::max<int64_t>(n, 1) * sizeof(double)));
         HIPCHK(c, launch_spmv(lsv_in(spmv_in(A, &A->tiles, sx.d), A), EPI_PLAIN, t.as<double>(), nullptr, BjOp{}, nullptr,
                               nullptr, nullptr, nullptr, 0, c->stream));
-        HIPCHK(c, launch_bj_apply(bj_op(M), n, t.as<double>(), sw.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0,
-                                  c->stream));
+        TRY(prec_apply(c, M, n, t.as<double>(), sw.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0, nullptr));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // t is freed on return
     }
     return stage_out(c, w, sw, n, kind);
@@ -664,6 +698,16 @@ int vtk_prec_refresh(vtk_prec *M, int64_t *epoch) {
     vtk_csr *A = M->A;
     vtk_ctx *c = A->ctx;
     HIPCHK(c, hipSetDevice(c->device));
+    if (M->kind == VTK_PREC_NEUMANN) {   // the wrapper owns no factors: its base's refresh, its base's epoch
+        if (!prec_alive(M->base, M->base_id))
+            return fail(c, VTK_ERR_STATE, "vtk_prec_refresh: the Neumann wrapper's base preconditioner has been destroyed");
+        int64_t eb = M->base->epoch;
+        const int rc = vtk_prec_refresh(M->base, &eb);
+        M->epoch = M->base->epoch;
+        M->valid = M->base->valid;
+        if (epoch) *epoch = M->epoch;
+        return rc;
+    }
     // the factors are overwritten from the first launch on: M is invalid until they are whole again
     const int64_t e = A->values_epoch;
     const int rc = M->kind == VTK_PREC_LINEC ? linec_factor(M) : M->kind == VTK_PREC_LINE2 ? line2_factor(M) : M->kind == VTK_PREC_LINE ? line_factor(M) : bj_factor(M);
@@ -704,8 +748,10 @@ int vtk_bjacobi_apply(vtk_prec *M, const double *r, double *z, int kind) {
     Staged sr, sz;
     TRY(stage_in(c, r, n, kind, sr));
     TRY(stage_in(c, kind == VTK_PTR_DEVICE ? z : nullptr, n, kind, sz));
+    if (M->kind == VTK_PREC_NEUMANN && kind == VTK_PTR_DEVICE && r == z)
+        return fail(c, VTK_ERR_ARG, "vtk_prec_apply: a Neumann wrapper cannot apply in place (r and z alias)");
     { Prof pf(c, prec_cls(M), -1, bj_row_bytes(M) * n + 16.0 * n);
-      HIPCHK(c, launch_bj_apply(bj_op(M), n, sr.d, sz.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0, c->stream)); }
+      TRY(prec_apply(c, M, n, sr.d, sz.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0, nullptr)); }
     return stage_out(c, z, sz, n, kind);
 }
 
@@ -762,7 +808,9 @@ int vtk_bjacobi_get_mode(vtk_prec *M, int *mode_in_use, int *tridiag_available) 
 
 void vtk_prec_destroy(vtk_prec *M) {
     if (!M) return;
+    prec_unregister(M);   // (a Neumann wrapper that borrowed M finds it gone; its own base is left alone)
     (void)hipSetDevice(M->device);
+    (void)hipFree(M->d_neu);
     (void)hipFree(M->d_inv);
     (void)hipFree(M->d_tri);
     (void)hipFree(M->line.f);

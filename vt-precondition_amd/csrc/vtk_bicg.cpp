@@ -85,8 +85,7 @@ struct Bicg {
     }
     int apply(const double *in, double *out, int tag) {
         Prof pf(c, prec_cls(M), tag, b_inv + 2 * n8);
-        BSOFT(launch_bj_apply(bj, n, in, out, nullptr, nullptr, nullptr, G, stop, tag, c->stream));
-        return VTK_OK;
+        return prec_apply(c, M, n, in, out, nullptr, nullptr, nullptr, G, stop, tag, &vote);
     }
 
     // the work vectors (across ranks a failed allocation is voted into the first all-reduce, which

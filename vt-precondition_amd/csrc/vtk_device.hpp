@@ -263,6 +263,16 @@ struct LineDc {
     const double *p;
     double *part;
 };
+// ACC instantiations of the sweep kernels (the Neumann wrapper's correction): the
+// sweep's last write stores acc[k] + z[k] instead of z[k]; the partials and the DCD dots are those
+// of the stored sum.  A type of its own, so that the other instantiations keep their arguments.
+struct LineDcAcc : LineDc {
+    const double *acc;
+};
+template <bool ACC>
+struct LineDcOf { using type = LineDc; };
+template <>
+struct LineDcOf<true> { using type = LineDcAcc; };
 
 // The basis vector an MGS step subtracts (and the basis read by the x update) is loaded
 // non-temporal, 16 B per lane, so that w stays resident in the 256 MB Infinity Cache across

@@ -124,6 +124,10 @@ inline void prof_flush(vtk_ctx *c, int last_col = 1 << 30) {
 inline BjOp bj_op(const vtk_prec *M) {
     BjOp o;
     if (!M) return o;
+    if (M->kind == VTK_PREC_NEUMANN) {   // the wrapper: a host routine (prec_apply), no single launch
+        o.neumann = true;
+        return o;
+    }
     if (M->kind == VTK_PREC_LINEC) {   // periodic whole lines: the three phases (launch_bj_apply)
         o.linec = &M->linec;
         return o;
@@ -156,8 +160,10 @@ inline bool bj8_tri(const vtk_prec *M) {
     return M && M->kind == VTK_PREC_BJACOBI && M->bs == 8 && bj_op(M).tri != nullptr;
 }
 
-// profile class of a standalone preconditioner apply
+// profile class of a standalone preconditioner apply (the Neumann wrapper brackets its own
+// launches: neu_resid, neu_corr and the base's class; a null name brackets nothing)
 inline const char *prec_cls(const vtk_prec *M) {
+    if (M && M->kind == VTK_PREC_NEUMANN) return nullptr;
     if (M && M->kind == VTK_PREC_LINEC) return "linec_apply";   // the three phases of the cyclic lines
     if (M && M->kind == VTK_PREC_LINE2) return "line2_apply";   // both sweeps of the product
     return M && M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply";
@@ -179,9 +185,26 @@ inline double linec_reduced_bytes(const LineC &C) {
 }
 inline double linec_correct_bytes(const LineC &C) { return 32.0 * (double)C.n + (C.nlev > 1 ? 8.0 * (double)C.lev[1].n : 0.0); }
 
+inline double solver_matrix_bytes(const vtk_csr *A);
+inline bool bj_fused(const vtk_prec *M);
+
+// the Neumann wrapper's corrections run in one SpMV launch each (EPI_NEU_CORR): a base with
+// BJ-fused tiles, bs <= 8 (tuning neu_fuse 0: the three-launch form, the same bits)
+inline bool neu_fused(const vtk_prec *N) {
+    return N && N->kind == VTK_PREC_NEUMANN && N->A->ctx->tune.neu_fuse && bj_fused(N->base) && N->base->bs <= 8;
+}
+
 // algorithmic bytes per row of one BJ application (tridiagonal: the SELL kernels read only m)
 inline double bj_row_bytes(const vtk_prec *M) {
     if (!M) return 0.0;
+    // the wrapper, less the r read and z written that the callers add: `degree` applications of the
+    // base; per correction the residual (the matrix, z and r read, t written), the base's own t read
+    // and u written, and the addition (z and u read, w written; fused into the base's last write
+    // where the kind allows -- the model keeps the unfused figure)
+    if (M->kind == VTK_PREC_NEUMANN) {
+        const double nn = (double)std::max<int64_t>(M->A->n_local, 1);
+        return M->degree * bj_row_bytes(M->base) + (M->degree - 1) * (solver_matrix_bytes(M->A) / nn + 24.0 + 16.0 + 24.0);
+    }
     if (M->kind == VTK_PREC_LINE) return line_row_bytes(M->line);
     // the cyclic lines: the three phases' bytes less the r read and z written that the callers add
     if (M->kind == VTK_PREC_LINEC)
@@ -443,6 +466,26 @@ int update_prepare(vtk_csr *A, UpdateScratch &u);
 int update_finish(vtk_csr *A, UpdateScratch &u);
 
 // ---- vtk_precond.cpp: factors from the operator's current values ------------------------------
+// the registry of live preconditioners: a Neumann wrapper borrows its base and finds out here
+// whether the base still exists (vtk_prec_destroy removes it)
+void prec_register(vtk_prec *M);
+void prec_unregister(const vtk_prec *M);
+bool prec_alive(const vtk_prec *M, uint64_t id);
+// DCGS2 step j's operands, for an apply that ends the step's operator (the wrapper's last correction
+// writes the dots partials in launch_dc_dots' layout where its kernels can: *cnt of them, else 0)
+struct StepDots {
+    const double *V;
+    int64_t ld;
+    int j;
+    double *part;
+};
+// z = M^-1 r for every kind: launch_bj_apply, or the Neumann wrapper's corrections (each with its
+// halo exchange).  part0 = sum z^2, part1 = sum v0 z over `grid` workgroups (optional).  vote: a
+// failed launch is voted (a solve across ranks); null: it returns at once.  r and z must not alias
+// for the wrapper
+int prec_apply(vtk_ctx *c, vtk_prec *M, int64_t n, const double *r, double *z, const double *v0, double *part0,
+               double *part1, int grid, const int *stop_col, int col, Vote *vote, const StepDots *dots = nullptr,
+               int *cnt = nullptr);
 int bj_factor(vtk_prec *M);
 int line_factor(vtk_prec *M);
 int line2_factor(vtk_prec *M);

@@ -105,6 +105,7 @@ struct StepPlan {
     bool ring0;      // step 0 of a band cycle through the x-line ring
     bool split;      // interior / boundary pieces of the fused step (world > 1)
     bool line_dc, line2_step, linec_step, line_lsv, line_canon, line_fuse;
+    bool neumann_step;   // the Neumann wrapper: SpMV, then its corrections (prec_apply)
     bool band_lsv, band_canon, band_nd;
     int band_opt;
     bool resid_fused, resid_g4, resid_ring;   // the cycle-end residual's kernel (residual())
@@ -143,6 +144,9 @@ StepPlan step_plan(const Solver &s) {
     P.line2_step = M && M->kind == VTK_PREC_LINE2 && M->line2.seg >= 1 && M->line2.seg <= 32 && s.G <= GMAX;
     // periodic whole lines: SpMV, the three apply phases, then the dots kernel
     P.linec_step = M && M->kind == VTK_PREC_LINEC && s.G <= GMAX;
+    // the Neumann wrapper: SpMV, z_1, the corrections; the last one with the step's dots
+    // where its kernel has that form (tuning neu_dc), else the dots kernel
+    P.neumann_step = M && M->kind == VTK_PREC_NEUMANN && s.G <= GMAX;
     // line path on a line-separable operator: the SpMV from the tables (VTK_BAND_LSV=0: SELL)
     P.line_lsv = (P.line_dc || P.line2_step || P.linec_step) && line_lsv_ok(c, A);
     P.ft = M ? &M->tiles : &A->tiles;
@@ -218,7 +222,7 @@ int precond_matvec(Solver &s, const StepPlan &P, const double *v, double *w, int
         { Prof pf(c, "spmv", col, b_csr + 2 * n8);
           HIPCHK(c, launch_spmv(lsv_in(spmv_in(A, &A->tiles, v), A), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, stop, col, c->stream)); }
         Prof pf(c, prec_cls(s.M), col, b_inv + 3 * n8);
-        HIPCHK(c, launch_bj_apply(bj_op(s.M), s.n, s.tmp, w, v0, s.part[0], s.part[1], s.G, stop, col, c->stream));
+        TRY(prec_apply(c, s.M, s.n, s.tmp, w, v0, s.part[0], s.part[1], s.G, stop, col, nullptr));
         cnt = s.G;
     }
     if (!want_dots) return VTK_OK;
@@ -352,6 +356,18 @@ int step_g4_ring(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt
     return VTK_OK;
 }
 
+// the Neumann wrapper: w = N^-1 (A p_j).  The SpMV in the solver's form (tables / grid rows where the
+// operator has them), then the wrapper's apply; cnt: the dots partials its last correction wrote
+int step_neumann(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
+    vtk_ctx *c = s.c;
+    vtk_csr *A = s.A;
+    TRY(halo_exchange(A, pj));
+    { Prof pf(c, "spmv", j, P.b_solver + 2 * P.n8);
+      SOFT(launch_spmv(lsv_in(spmv_in(A, &A->tiles, pj), A), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, s.stop, j, c->stream)); }
+    const StepDots dots{s.V, s.ld, j, s.dcpart};
+    return prec_apply(c, s.M, s.n, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, s.stop, j, &s.vote, &dots, &cnt);
+}
+
 // the form step j takes (the plan's order of precedence)
 int operator_step(Solver &s, const StepPlan &P, int j, double *pj, int &cnt) {
     const double b_step = P.b_solver + P.b_inv + P.n8 * (j + 2);   // matrix, BJ, p, w, V_j
@@ -364,6 +380,7 @@ int operator_step(Solver &s, const StepPlan &P, int j, double *pj, int &cnt) {
     if (P.fused) return step_fused(s, P, j, pj, b_step, cnt);
     if (P.line_dc || P.line2_step || P.linec_step) return step_line(s, P, j, pj, cnt);
     if (P.ring4) return step_g4_ring(s, P, j, pj, cnt);
+    if (P.neumann_step) return step_neumann(s, P, j, pj, cnt);
     Red h0, d0;
     return precond_matvec(s, P, pj, s.w, j, h0, d0, false);
 }
@@ -705,7 +722,7 @@ int initial_norms(Solver &s, bool &r_is_b) {
     HIPCHK(c, launch_finalize(rb, &ds->scal[0], 1, c->stream));
     // M b goes to V[0]: with x0 = 0 it is the first cycle's psolve(r) (run_gmres)
     { Prof pf(c, prec_cls(M), -1, bj_row_bytes(M) * n + 2 * n8);
-      HIPCHK(c, launch_bj_apply(bj_op(M), n, s.b, s.V, nullptr, s.part[1], nullptr, s.G, nullptr, 0, c->stream)); }
+      TRY(prec_apply(c, M, n, s.b, s.V, nullptr, s.part[1], nullptr, s.G, nullptr, 0, nullptr)); }
     TRY(reduce(c, s.part[1], s.G, rmb));
     HIPCHK(c, launch_finalize(rmb, &ds->scal[1], 1, c->stream));
     // `r = b - matvec(x) if x.any() else b.copy()` (iterative.py:737): any nonzero x0 on any rank
@@ -745,7 +762,7 @@ int run_cycle(Solver &s, const StepPlan &P, const Capture &cap, int64_t it, bool
     Red rv = rz;
     if (!r_ready) {
         { Prof pf(c, prec_cls(s.M), -1, P.b_inv + 2 * P.n8);
-          SOFT(launch_bj_apply(bj_op(s.M), n, s.r, s.V, nullptr, s.part[0], nullptr, s.G, nullptr, 0, c->stream)); }
+          TRY(prec_apply(c, s.M, n, s.r, s.V, nullptr, s.part[0], nullptr, s.G, nullptr, 0, &s.vote)); }
         TRY(reduce(c, s.part[0], s.G, rv));
     }
     { Prof pf(c, "scale0", -1, 2 * P.n8);

@@ -246,6 +246,11 @@ struct Tuning {
                               // k_bcg_p / k_bcg_s (0: the separate apply; the same bits either way)
     int linec_serial = 64;    // line_cyclic: a reduced level of at most this many unknowns per line is the
                               // last, solved by one lane per line (read at vtk_linecyclic_create)
+    int neu_fuse = 1;         // Neumann wrapper around a BJ-fused base (bs <= 8): each correction
+                              // w = z + M^-1 (r - A z) in one SpMV launch (0: residual SpMV, the base's
+                              // apply, the addition -- the same bits; A/B and tests)
+    int neu_dc = 1;           // Neumann wrapper, DCGS2 step: the step's dots behind the last correction's
+                              // addition (0: the plain addition, then launch_dc_dots; A/B and tests)
     int fail_step = -1;       // (test hook) >= 0: this rank's DCGS2 step of that index fails in the
                               // first cycle as a refused launch would (the peer-failure vote, vtk_gmres);
                               // vtk_bicgstab: the first launch of that loop index is refused
@@ -385,6 +390,14 @@ struct vtk_prec {
     int compact_req = -1;            // vtk_linejacobi_set_compact's last request (-1: none)
     int64_t epoch = 0;               // vtk_csr::values_epoch of the values M was factored from
     bool valid = true;               // false after a refresh that met a singular block / zero pivot
+    // Neumann-series wrapper (vtk_neumann_create): kind VTK_PREC_NEUMANN.  The base
+    // is borrowed, not owned: base_id is its serial in the registry of live preconditioners
+    // (vtk_precond.cpp), checked before every use.  d_neu: three work vectors of n_local doubles
+    uint64_t id = 0;                 // this preconditioner's serial in the registry (every kind)
+    vtk_prec *base = nullptr;
+    uint64_t base_id = 0;
+    int degree = 1;
+    double *d_neu = nullptr;
 };
 
 namespace vtk {
@@ -426,6 +439,9 @@ struct BjOp {
     const LineOp *line2 = nullptr;
     const double *diag = nullptr;
     const LineC *linec = nullptr;   // periodic whole lines instead (vtk_linecyclic_create)
+    // the Neumann wrapper: its apply needs the operator and its halo exchange, so
+    // it is a host routine (vtk_precond.cpp prec_apply); launch_bj_apply refuses it
+    bool neumann = false;
 };
 
 // mm[0] = min, mm[1] = max of idx[0..n) (mm preset to INT_MAX, INT_MIN)
@@ -436,11 +452,17 @@ inline int spmv_grid(const SpmvIn &in) { return (in.sell && in.groups) ? in.grou
 
 // EPI_PREC_DC: w = M^-1 A p_j plus the DCGS2 step's dot products (launch_spmv_dc)
 // EPI_PREC_DC_ND (launch_lsv_ring_epi only): EPI_PREC_DC as w = p_j + M^-1 (A - M) p_j, D not read
-enum Epi { EPI_PLAIN = 0, EPI_RESID = 1, EPI_PREC = 2, EPI_RESID_PREC = 3, EPI_PREC_DC = 4, EPI_PREC_DC_ND = 5 };
+// EPI_NEU_RESID: y = b - A x and nothing else (the Neumann wrapper's residual)
+// EPI_NEU_CORR: y = x + M^-1 (b - A x), one correction of the wrapper in one launch (BJ-fused tiles,
+// bs <= 8; tridiagonal blocks solved with the stored l | m | g, as launch_bj_apply does)
+enum Epi { EPI_PLAIN = 0, EPI_RESID = 1, EPI_PREC = 2, EPI_RESID_PREC = 3, EPI_PREC_DC = 4, EPI_PREC_DC_ND = 5,
+           EPI_NEU_RESID = 6, EPI_NEU_CORR = 7 };
 
 // y = A x (PLAIN); y = b - A x, part0 = sum y^2 (RESID); y = M^-1 A x with M = BJ(inv, bs)
 // or identity (inv == null), part0 = sum y^2, part1 = sum v0*y (PREC, v0 may be null);
 // RESID_PREC: r = b - A x, y = M^-1 r, part0 = sum r^2, part1 = sum y^2.
+// NEU_RESID: y = b - A x, no partials.  NEU_CORR: y = x + M^-1 (b - A x) (y must not alias x);
+// part0 = sum y^2 and part1 = sum v0*y when part0 is given (the wrapper's last correction).
 hipError_t launch_spmv(const SpmvIn &in, int epi, double *y, const double *b, const BjOp &bj,
                        const double *v0, double *part0, double *part1,
                        const int *stop_col, int col, hipStream_t s);
@@ -469,14 +491,19 @@ hipError_t launch_line_setup(const int32_t *indptr, const int32_t *indices, cons
                              const LineOp &L, unsigned long long *bad_row, unsigned long long *ext, hipStream_t s);
 // z = M_line^-1 r fused with DCGS2 step j's dots (p = the SpMV input, partials in the
 // launch_dc_dots layout); hipErrorInvalidValue when the segments are too long (> 32)
+// zadd (here and in the sweeps below; the Neumann wrapper's correction): the last
+// write stores zadd + M^-1 r instead, and the partials / dots are those of the stored sum; the
+// output must not alias zadd
 hipError_t launch_line_dc(const LineOp &L, const double *r, double *w, const double *V, int64_t ld, int j,
-                          const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s);
+                          const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s,
+                          const double *zadd = nullptr);
 // the same with y = A p formed inside (k_line_spmv_dc): one rank, canonical line-separable rows
 // (lsv: vtk_csr::d_lsv), lines of L.stride rows, compact factors; hipErrorInvalidValue otherwise
 hipError_t launch_line_spmv_dc(const LineOp &L, const double *lsv, const double *p, double *w, const double *V,
                                int64_t ld, int j, double *part, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_line_apply(const LineOp &L, const double *r, double *z, const double *v0, double *part0,
-                             double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+                             double *part1, int grid, const int *stop_col, int col, hipStream_t s,
+                             const double *zadd = nullptr);
 // line product, second sweep (vtk_line2.hip): z = M_L^-1 (D t), the forward sweep's right-hand side
 // formed as D[k] t[k] per row; t and z may alias.  Partials as launch_line_apply / launch_line_dc
 // (the DCD form: segments <= 32, else hipErrorInvalidValue).  launch_line2_diag: D[r] = the sum of
@@ -484,9 +511,11 @@ hipError_t launch_line_apply(const LineOp &L, const double *r, double *z, const 
 hipError_t launch_line2_diag(const int32_t *indptr, const int32_t *indices, const void *data, int fp32, int64_t n,
                              double *D, hipStream_t s);
 hipError_t launch_line2_apply(const LineOp &L, const double *D, const double *t, double *z, const double *v0,
-                              double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+                              double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s,
+                              const double *zadd = nullptr);
 hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, double *w, const double *V, int64_t ld,
-                           int j, const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s);
+                           int j, const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s,
+                           const double *zadd = nullptr);
 // periodic whole lines (vtk_linec.hip).  launch_linec_setup: level lev's factors and spikes (level
 // 0 from the CSR, else from co = a | b | c), then its separators' system into co (the next level's
 // coefficients) or, at the last level, C.minv; bad[lev] / bad[nlev]: the smallest element index of
@@ -497,9 +526,18 @@ hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, do
 hipError_t launch_linec_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
                               const LineC &C, int lev, double *co, unsigned long long *bad, hipStream_t s);
 hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double *z, const double *v0, double *part0,
-                              double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+                              double *part1, int grid, const int *stop_col, int col, hipStream_t s,
+                              const double *zadd = nullptr);   // (zadd: phase 2 only)
 hipError_t launch_linec_apply(const LineC &C, const double *r, double *z, const double *v0, double *part0,
                               double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+// Neumann wrapper (vtk_neumann.hip): w = z + u, one addition per row, with
+// part0 = sum w^2 and part1 = sum v0 w (optional) over `grid` workgroups; w may alias z or u.
+// launch_neu_add_dc: the same addition with DCGS2 step j's dots behind it (p = V[j], the partials in
+// launch_dc_dots' layout), so that no dots kernel re-reads w
+hipError_t launch_neu_add(const double *z, const double *u, double *w, int64_t n, const double *v0, double *part0,
+                          double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+hipError_t launch_neu_add_dc(const double *z, const double *u, double *w, int64_t n, const double *V, int64_t ld,
+                             int j, double *part, int grid, const int *stop_col, int col, hipStream_t s);
 hipError_t launch_bj_tri_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
                                int64_t n, int bs, const double *inv, double *tri, int64_t ld, int *flags,
                                hipStream_t s);

@@ -183,19 +183,21 @@ __device__ __forceinline__ double row_epilogue(const SpmvK<VT, HALO> &a, double 
     if constexpr (EPI == EPI_PLAIN) {
         if (act) st_nt<2>(a.y + row, s);
         return s;
-    } else if constexpr (EPI == EPI_RESID) {
+    } else if constexpr (EPI == EPI_RESID || EPI == EPI_NEU_RESID) {
+        // NEU_RESID: the row sum rounded to double, then one subtraction; no partials
         const double r = act ? (have_bv ? bv : a.b[row]) - s : 0.0;
         if (act) {
             st_nt<2>(a.y + row, r);
-            acc0 += r * r;
+            if constexpr (EPI == EPI_RESID) acc0 += r * r;
         }
         return r;
     } else {
         // PREC: z = M^-1 (A x);  RESID_PREC: r = b - A x (iterative.py:816), z = M^-1 r
+        // NEU_CORR: r = b - A x, u = M^-1 r, y = x + u (one addition per row)
         double sv = s;
-        if constexpr (EPI == EPI_RESID_PREC) {
+        if constexpr (EPI == EPI_RESID_PREC || EPI == EPI_NEU_CORR) {
             sv = act ? (have_bv ? bv : a.b[row]) - s : 0.0;
-            acc0 += sv * sv;
+            if constexpr (EPI == EPI_RESID_PREC) acc0 += sv * sv;
         }
         double z = sv;
         if constexpr (BS > 0 && TRI && TRIM) {
@@ -216,12 +218,18 @@ __device__ __forceinline__ double row_epilogue(const SpmvK<VT, HALO> &a, double 
             }
         }
         if (act) {
+            if constexpr (EPI == EPI_NEU_CORR) z = a.x[row] + z;
             if (store) {
                 if constexpr (DC) __builtin_nontemporal_store(z, a.y + row);   // (A/B: fused 593 -> 582 us)
                 else st_nt<2>(a.y + row, z);
             }
             if constexpr (EPI == EPI_RESID_PREC) {
                 acc1 += z * z;
+            } else if constexpr (EPI == EPI_NEU_CORR) {
+                if (a.part0) {   // the wrapper's last correction: |y|^2 and v0.y
+                    acc0 += z * z;
+                    if (a.v0) acc1 += a.v0[row] * z;
+                }
             } else if constexpr (!DC) {
                 acc0 += z * z;
                 if (a.v0) acc1 += (have_bv ? v0v : a.v0[row]) * z;
@@ -322,6 +330,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
                         const double r = a.b[row] - s;
                         a.y[row] = r;
                         acc0 += r * r;
+                    } else if constexpr (EPI == EPI_NEU_RESID) {
+                        a.y[row] = a.b[row] - s;
+                    } else if constexpr (EPI == EPI_NEU_CORR) {
+                        // (BJ-fused tiles never hold long rows: launch_spmv refuses BS == 0)
                     } else if constexpr (EPI == EPI_RESID_PREC) {
                         const double r = a.b[row] - s;   // BS == 0 only (host guarantees)
                         a.y[row] = r;
@@ -340,7 +352,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
         dc_write(dc, a.j, prod, a.dcpart);
         return;
     }
-    if constexpr (EPI != EPI_PLAIN && !DC) {
+    if constexpr (EPI == EPI_NEU_CORR) {
+        if (a.part0) {   // (uniform: a kernel argument)
+            const double t0 = block_sum(acc0, red);
+            if (tid == 0) a.part0[blockIdx.x] = t0;
+            if (a.v0) {
+                const double t1 = block_sum(acc1, red);
+                if (tid == 0) a.part1[blockIdx.x] = t1;
+            }
+        }
+    } else if constexpr (EPI != EPI_PLAIN && EPI != EPI_NEU_RESID && !DC) {
         const double t0 = block_sum(acc0, red);
         if (tid == 0) a.part0[blockIdx.x] = t0;
         if (EPI == EPI_RESID_PREC || (EPI == EPI_PREC && a.v0 != nullptr)) {
@@ -414,7 +435,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELL_WPE))) 
         const bool act = row < a.n_local;
         double s = 0.0;
         double sub = 0.0, sup = 0.0;   // TRI: the row's block sub/super-diagonal entries
-        constexpr bool TRIM = TRI && BS > 0;
+        // (NEU_CORR solves with the stored l | m | g, the bits of launch_bj_apply: DESIGN.md §3n)
+        constexpr bool TRIM = TRI && BS > 0 && EPI != EPI_NEU_CORR;
         [[maybe_unused]] const int ii = lane & (BS > 0 ? BS - 1 : 0);
         // HOIST: the row's own operands (BJ factor m, p, b, v0) issued ahead of the CSR loads,
         // so the epilogue does not wait a memory round trip per chunk (EPI_PREC: 352 -> ... us)
@@ -427,7 +449,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELL_WPE))) 
         } else if constexpr (HOISTE) {
             if (act) {
                 if constexpr (TRIM) mrow = ld_nt<1>(a.tri + a.tri_ld + row);
-                if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_PREC) bv = a.b[row];
+                if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_PREC || EPI == EPI_NEU_RESID || EPI == EPI_NEU_CORR) bv = a.b[row];
                 if constexpr (EPI == EPI_PREC) {
                     if (a.v0) v0v = a.v0[row];
                 }
@@ -780,7 +802,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SELL_WPE))) 
         }
         return;
     }
-    if constexpr (EPI != EPI_PLAIN) {
+    if constexpr (EPI == EPI_NEU_CORR) {
+        if (a.part0) {   // (uniform: a kernel argument)
+            const double t0 = block_sum(acc0, red);
+            if (tid == 0) a.part0[blockIdx.x] = t0;
+            if (a.v0) {
+                const double t1 = block_sum(acc1, red);
+                if (tid == 0) a.part1[blockIdx.x] = t1;
+            }
+        }
+    } else if constexpr (EPI != EPI_PLAIN && EPI != EPI_NEU_RESID) {
         const double t0 = block_sum(acc0, red);
         if (tid == 0) a.part0[blockIdx.x] = t0;
         if (EPI == EPI_RESID_PREC || (EPI == EPI_PREC && a.v0 != nullptr)) {
@@ -1019,7 +1050,18 @@ static hipError_t spmv_dispatch(const SpmvIn &in, int epi, double *y, const doub
         VTK_SPMV_LAUNCH(EPI_RESID, 1, false);
         return hipGetLastError();
     }
+    if (epi == EPI_NEU_RESID) {
+        VTK_SPMV_LAUNCH(EPI_NEU_RESID, 1, false);
+        return hipGetLastError();
+    }
+    if (epi == EPI_NEU_CORR) {
+        // BJ-fused tiles with bs in {1, 2, 4, 8} only (the caller runs the unfused correction
+        // otherwise); y is written while other workgroups still gather x
+        if (bs < 1 || bs > 8 || y == in.x) return hipErrorInvalidValue;
+        return launch_bj_variant<VT, HALO, EPI_NEU_CORR, 8>(a, bs, tri, sell, g, s);
+    }
     if (epi == EPI_PREC) return launch_bj_variant<VT, HALO, EPI_PREC, 32>(a, bs, tri, sell, g, s);
+    if (epi != EPI_RESID_PREC) return hipErrorInvalidValue;
     return launch_bj_variant<VT, HALO, EPI_RESID_PREC, 32>(a, bs, tri, sell, g, s);
 }
 
@@ -1153,6 +1195,7 @@ __global__ __launch_bounds__(NT) void k_bj_apply_tri(const double *__restrict__ 
 hipError_t launch_bj_apply(const BjOp &bj, int64_t n, const double *r, double *z,
                            const double *v0, double *part0, double *part1, int grid,
                            const int *stop_col, int col, hipStream_t s) {
+    if (bj.neumann) return hipErrorInvalidValue;   // the wrapper applies through vtk::prec_apply (host)
     if (bj.linec) return launch_linec_apply(*bj.linec, r, z, v0, part0, part1, grid, stop_col, col, s);
     if (bj.line && bj.line2) {
         // line product: t = M1^-1 r into z, then z = M2^-1 (D t) in place
@@ -1369,11 +1412,13 @@ __global__ __launch_bounds__(NT) void k_line_setup(const int32_t *__restrict__ i
 // lane's registers, p and the basis rows of the lane's segment rows are read once here:
 // s = V_j^T p, z = V_j^T w, ||p||^2, p.w, ||w||^2 as per-workgroup partials in launch_dc_dots'
 // layout (dc.part[q * GMAX + block]); no separate dots kernel re-reads w.
-template <int LMAX, bool COMPACT, bool DCD = false>
+// ACC (the Neumann wrapper's correction): the backward sweep stores dc.acc[k] + z[k];
+// the recurrence keeps z, the partials and the DCD dots take the stored sum.  z must not alias acc.
+template <int LMAX, bool COMPACT, bool DCD = false, bool ACC = false>
 __global__ __launch_bounds__(NT) void k_line_apply(LineOp L, const double *r, double *z,
                                                    const double *__restrict__ v0, double *part0,
                                                    double *part1, const int *stop_col, int col,
-                                                   LineDc dc = LineDc{}) {
+                                                   typename LineDcOf<ACC>::type dc = {}) {
     __shared__ double red[NT / 64];
     constexpr int NQW = 2 * DC_MAXJ + 3;
     __shared__ double stage[DCD ? (NT / 64) * NQW : 1];
@@ -1431,6 +1476,21 @@ __global__ __launch_bounds__(NT) void k_line_apply(LineOp L, const double *r, do
 #pragma unroll
             for (int u = LMAX - 1; u >= 0; --u) {
                 const double zv = e[u] - gg[u] * zn;
+                if constexpr (ACC) {
+                    double zo = 0.0;   // the row's output: acc + z
+                    if ((okm >> u) & 1u) {
+                        const int k = (int)(k0l + (int64_t)u * S);
+                        zo = dc.acc[k] + zv;
+                        st_nt<4>(z + k, zo);
+                        zn = zv;
+                        if constexpr (!DCD) {
+                            acc0 += zo * zo;
+                            if (v0) acc1 += v0[k] * zo;
+                        }
+                    }
+                    if constexpr (DCD) e[u] = zo;
+                    continue;
+                }
                 if ((okm >> u) & 1u) {
                     const int k = (int)(k0l + (int64_t)u * S);
                     st_nt<4>(z + k, zv);
@@ -1490,6 +1550,14 @@ __global__ __launch_bounds__(NT) void k_line_apply(LineOp L, const double *r, do
                 if (!q.jv || R < r0 || R >= r_end) continue;
                 const int64_t k = R - r0;
                 const double zv = m[k] * z[k] - g[k] * zn;
+                if constexpr (ACC) {
+                    const double zo = dc.acc[k] + zv;
+                    z[k] = zo;
+                    zn = zv;
+                    acc0 += zo * zo;
+                    if (v0) acc1 += v0[k] * zo;
+                    continue;
+                }
                 z[k] = zv;
                 zn = zv;
                 acc0 += zv * zv;
@@ -1735,10 +1803,25 @@ hipError_t launch_line_setup(const int32_t *indptr, const int32_t *indices, cons
 // line apply + DCGS2 dots of step j (segments <= 32; else hipErrorInvalidValue: the caller
 // runs the unfused dots)
 hipError_t launch_line_dc(const LineOp &L, const double *r, double *w, const double *V, int64_t ld, int j,
-                          const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s) {
-    if (j > DC_MAXJ || grid > GMAX || L.seg > 32 || L.seg <= 0) return hipErrorInvalidValue;
+                          const double *p, double *part, int grid, const int *stop_col, int col, hipStream_t s,
+                          const double *zadd) {
+    if (j > DC_MAXJ || grid > GMAX || L.seg > 32 || L.seg <= 0 || zadd == w) return hipErrorInvalidValue;
     const dim3 g(grid), b(NT);
     const LineDc dc{V, ld, j, p, part};
+    if (zadd) {   // w = zadd + M^-1 r and the dots of that w
+        const LineDcAcc da{dc, zadd};
+#define VTK_LINE_DCA_LAUNCH(LM)                                                                              \
+    do {                                                                                                     \
+        if (L.compact) hipLaunchKernelGGL((k_line_apply<LM, true, true, true>), g, b, 0, s, L, r, w, nullptr, nullptr, nullptr, stop_col, col, da); \
+        else hipLaunchKernelGGL((k_line_apply<LM, false, true, true>), g, b, 0, s, L, r, w, nullptr, nullptr, nullptr, stop_col, col, da);        \
+    } while (0)
+        if (L.seg <= 8) VTK_LINE_DCA_LAUNCH(8);
+        else if (L.seg <= 16) VTK_LINE_DCA_LAUNCH(16);
+        else if (L.seg <= 25) VTK_LINE_DCA_LAUNCH(25);
+        else VTK_LINE_DCA_LAUNCH(32);
+#undef VTK_LINE_DCA_LAUNCH
+        return hipGetLastError();
+    }
 #define VTK_LINE_DC_LAUNCH(LM)                                                                               \
     do {                                                                                                     \
         if (L.compact) hipLaunchKernelGGL((k_line_apply<LM, true, true>), g, b, 0, s, L, r, w, nullptr, nullptr, nullptr, stop_col, col, dc); \
@@ -1753,10 +1836,26 @@ hipError_t launch_line_dc(const LineOp &L, const double *r, double *w, const dou
 }
 
 hipError_t launch_line_apply(const LineOp &L, const double *r, double *z, const double *v0, double *part0,
-                             double *part1, int grid, const int *stop_col, int col, hipStream_t s) {
+                             double *part1, int grid, const int *stop_col, int col, hipStream_t s, const double *zadd) {
     if (L.n == 0 && part0 == nullptr) return hipSuccess;
     const dim3 g(grid), b(NT);
-#define VTK_LINE_LAUNCH(LM)                                                                                  \
+    if (zadd) {   // z = zadd + M^-1 r
+        if (zadd == z) return hipErrorInvalidValue;
+        const LineDcAcc da{LineDc{}, zadd};
+#define VTK_LINE_ACC_LAUNCH(LM)                                                                              \
+    do {                                                                                                     \
+        if (L.compact) hipLaunchKernelGGL((k_line_apply<LM, true, false, true>), g, b, 0, s, L, r, z, v0, part0, part1, stop_col, col, da); \
+        else hipLaunchKernelGGL((k_line_apply<LM, false, false, true>), g, b, 0, s, L, r, z, v0, part0, part1, stop_col, col, da);        \
+    } while (0)
+        if (L.seg <= 8) VTK_LINE_ACC_LAUNCH(8);
+        else if (L.seg <= 16) VTK_LINE_ACC_LAUNCH(16);
+        else if (L.seg <= 25) VTK_LINE_ACC_LAUNCH(25);
+        else if (L.seg <= 32) VTK_LINE_ACC_LAUNCH(32);
+        else hipLaunchKernelGGL((k_line_apply<0, false, false, true>), g, b, 0, s, L, r, z, v0, part0, part1, stop_col, col, da);
+#undef VTK_LINE_ACC_LAUNCH
+        return hipGetLastError();
+    }
+#define VTK_LINE_LAUNCH(LM)                                                                                 \
     do {                                                                                                     \
         if (L.compact) hipLaunchKernelGGL((k_line_apply<LM, true>), g, b, 0, s, L, r, z, v0, part0, part1, stop_col, col); \
         else hipLaunchKernelGGL((k_line_apply<LM, false>), g, b, 0, s, L, r, z, v0, part0, part1, stop_col, col);        \

@@ -36,11 +36,12 @@ __global__ __launch_bounds__(NT) void k_line2_diag(const int32_t *__restrict__ i
 // read, 24 B/row, and z written.  LMAX == 0 (segments longer than 32): d goes through z.  t and
 // z may alias (each row is read before it is written, by its lane).
 // DCD: the DCGS2 step's dots behind the sweep, in k_line_apply<.., true>'s partial layout.
-template <int LMAX, bool COMPACT, bool DCD = false>
+// ACC: the backward sweep stores dc.acc[k] + z[k] (k_line_apply's ACC; z must not alias acc).
+template <int LMAX, bool COMPACT, bool DCD = false, bool ACC = false>
 __global__ __launch_bounds__(NT) void k_line2_apply(LineOp L, const double *__restrict__ D, const double *t_in,
                                                     double *z, const double *__restrict__ v0, double *part0,
                                                     double *part1, const int *stop_col, int col,
-                                                    LineDc dc = LineDc{}) {
+                                                    typename LineDcOf<ACC>::type dc = {}) {
     __shared__ double red[NT / 64];
     constexpr int NQW = 2 * DC_MAXJ + 3;
     __shared__ double stage[DCD ? (NT / 64) * NQW : 1];
@@ -99,6 +100,21 @@ __global__ __launch_bounds__(NT) void k_line2_apply(LineOp L, const double *__re
 #pragma unroll
             for (int u = LMAX - 1; u >= 0; --u) {
                 const double zv = e[u] - gg[u] * zn;
+                if constexpr (ACC) {
+                    double zo = 0.0;   // the row's output: acc + z
+                    if ((okm >> u) & 1u) {
+                        const int k = (int)(k0l + (int64_t)u * S);
+                        zo = dc.acc[k] + zv;
+                        st_nt<4>(z + k, zo);
+                        zn = zv;
+                        if constexpr (!DCD) {
+                            acc0 += zo * zo;
+                            if (v0) acc1 += v0[k] * zo;
+                        }
+                    }
+                    if constexpr (DCD) e[u] = zo;
+                    continue;
+                }
                 if ((okm >> u) & 1u) {
                     const int k = (int)(k0l + (int64_t)u * S);
                     st_nt<4>(z + k, zv);
@@ -158,6 +174,14 @@ __global__ __launch_bounds__(NT) void k_line2_apply(LineOp L, const double *__re
                 if (!q.jv || R < r0 || R >= r_end) continue;
                 const int64_t k = R - r0;
                 const double zv = m[k] * z[k] - g[k] * zn;
+                if constexpr (ACC) {
+                    const double zo = dc.acc[k] + zv;
+                    z[k] = zo;
+                    zn = zv;
+                    acc0 += zo * zo;
+                    if (v0) acc1 += v0[k] * zo;
+                    continue;
+                }
                 z[k] = zv;
                 zn = zv;
                 acc0 += zv * zv;
@@ -211,10 +235,24 @@ hipError_t launch_line2_diag(const int32_t *indptr, const int32_t *indices, cons
 
 hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, double *w, const double *V, int64_t ld,
                            int j, const double *p, double *part, int grid, const int *stop_col, int col,
-                           hipStream_t s) {
-    if (j > DC_MAXJ || grid > GMAX || L.seg > 32 || L.seg <= 0 || !D) return hipErrorInvalidValue;
+                           hipStream_t s, const double *zadd) {
+    if (j > DC_MAXJ || grid > GMAX || L.seg > 32 || L.seg <= 0 || !D || zadd == w) return hipErrorInvalidValue;
     const dim3 g(grid), b(NT);
     const LineDc dc{V, ld, j, p, part};
+    if (zadd) {   // w = zadd + M_L^-1 (D t) and the dots of that w
+        const LineDcAcc da{dc, zadd};
+#define VTK_LINE2_DCA_LAUNCH(LM)                                                                             \
+    do {                                                                                                     \
+        if (L.compact) hipLaunchKernelGGL((k_line2_apply<LM, true, true, true>), g, b, 0, s, L, D, t, w, nullptr, nullptr, nullptr, stop_col, col, da); \
+        else hipLaunchKernelGGL((k_line2_apply<LM, false, true, true>), g, b, 0, s, L, D, t, w, nullptr, nullptr, nullptr, stop_col, col, da);        \
+    } while (0)
+        if (L.seg <= 8) VTK_LINE2_DCA_LAUNCH(8);
+        else if (L.seg <= 16) VTK_LINE2_DCA_LAUNCH(16);
+        else if (L.seg <= 25) VTK_LINE2_DCA_LAUNCH(25);
+        else VTK_LINE2_DCA_LAUNCH(32);
+#undef VTK_LINE2_DCA_LAUNCH
+        return hipGetLastError();
+    }
 #define VTK_LINE2_DC_LAUNCH(LM)                                                                              \
     do {                                                                                                     \
         if (L.compact) hipLaunchKernelGGL((k_line2_apply<LM, true, true>), g, b, 0, s, L, D, t, w, nullptr, nullptr, nullptr, stop_col, col, dc); \
@@ -229,10 +267,27 @@ hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, do
 }
 
 hipError_t launch_line2_apply(const LineOp &L, const double *D, const double *t, double *z, const double *v0,
-                              double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s) {
+                              double *part0, double *part1, int grid, const int *stop_col, int col, hipStream_t s,
+                              const double *zadd) {
     if (L.n == 0 && part0 == nullptr) return hipSuccess;
     if (!D || grid < 1) return hipErrorInvalidValue;
     const dim3 g(grid), b(NT);
+    if (zadd) {   // z = zadd + M_L^-1 (D t)
+        if (zadd == z) return hipErrorInvalidValue;
+        const LineDcAcc da{LineDc{}, zadd};
+#define VTK_LINE2_ACC_LAUNCH(LM)                                                                             \
+    do {                                                                                                     \
+        if (L.compact) hipLaunchKernelGGL((k_line2_apply<LM, true, false, true>), g, b, 0, s, L, D, t, z, v0, part0, part1, stop_col, col, da); \
+        else hipLaunchKernelGGL((k_line2_apply<LM, false, false, true>), g, b, 0, s, L, D, t, z, v0, part0, part1, stop_col, col, da);        \
+    } while (0)
+        if (L.seg <= 8) VTK_LINE2_ACC_LAUNCH(8);
+        else if (L.seg <= 16) VTK_LINE2_ACC_LAUNCH(16);
+        else if (L.seg <= 25) VTK_LINE2_ACC_LAUNCH(25);
+        else if (L.seg <= 32) VTK_LINE2_ACC_LAUNCH(32);
+        else hipLaunchKernelGGL((k_line2_apply<0, false, false, true>), g, b, 0, s, L, D, t, z, v0, part0, part1, stop_col, col, da);
+#undef VTK_LINE2_ACC_LAUNCH
+        return hipGetLastError();
+    }
 #define VTK_LINE2_LAUNCH(LM)                                                                                 \
     do {                                                                                                     \
         if (L.compact) hipLaunchKernelGGL((k_line2_apply<LM, true>), g, b, 0, s, L, D, t, z, v0, part0, part1, stop_col, col); \

@@ -393,6 +393,68 @@ __global__ __launch_bounds__(NT) void k_linec_correct(LcView L, double *z, const
     }
 }
 
+// the same pass storing acc + z (level 0 only; the Neumann wrapper's correction): one
+// more addition per row, the partials those of the stored sum.  z must not alias acc.  (A kernel
+// of its own: k_linec_correct keeps its code.)
+template <int LQ>
+__global__ __launch_bounds__(NT) void k_linec_correct_acc(LcView L, double *z, const double *__restrict__ xs,
+                                                          const double *__restrict__ v0, double *part0, double *part1,
+                                                          const int *stop_col, int col, const double *__restrict__ acc) {
+    __shared__ double red[NT / 64];
+    if (stopped(stop_col, col)) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t nitems = L.nblk * L.nseg * L.jb, S = L.S;
+    const double *V = L.f + 3 * L.n, *W = L.f + 4 * L.n;
+    double acc0 = 0.0, acc1 = 0.0;
+    for (int64_t t = (int64_t)blockIdx.x * (NT / 64) + wv; t < nitems; t += (int64_t)gridDim.x * (NT / 64)) {
+        const LcLane q = lc_lane(L, t, lane);
+        if (!q.jv) continue;
+        const int nq = q.len - 1;
+        const double xi = xs[q.left], eta = xs[q.sidx];
+        if constexpr (LQ > 0) {
+            double y[LQ], vv[LQ], ww[LQ];
+#pragma unroll
+            for (int u = 0; u < LQ; ++u) {
+                const int k = u < nq ? (int)(q.base + (int64_t)u * S) : 0;
+                y[u] = ld_nt<8>(z + k);
+                vv[u] = ld_nt<8>(V + k);
+                ww[u] = ld_nt<8>(W + k);
+            }
+#pragma unroll
+            for (int u = 0; u < LQ; ++u) {
+                if (u < nq) {
+                    const int k = (int)(q.base + (int64_t)u * S);
+                    const double zv = acc[k] + ((y[u] - vv[u] * xi) - ww[u] * eta);
+                    st_nt<4>(z + k, zv);
+                    acc0 += zv * zv;
+                    if (v0) acc1 += v0[k] * zv;
+                }
+            }
+        } else {
+            for (int u = 0; u < nq; ++u) {
+                const int64_t k = q.base + (int64_t)u * S;
+                const double zv = acc[k] + ((z[k] - V[k] * xi) - W[k] * eta);
+                z[k] = zv;
+                acc0 += zv * zv;
+                if (v0) acc1 += v0[k] * zv;
+            }
+        }
+        const int64_t s = q.base + (int64_t)nq * S;
+        const double zs = acc[s] + eta;
+        z[s] = zs;
+        acc0 += zs * zs;
+        if (v0) acc1 += v0[s] * zs;
+    }
+    if (part0) {
+        const double t0 = block_sum(acc0, red);
+        if (threadIdx.x == 0) part0[blockIdx.x] = t0;
+    }
+    if (part1 && v0) {
+        const double t1 = block_sum(acc1, red);
+        if (threadIdx.x == 0) part1[blockIdx.x] = t1;
+    }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------
 static int lc_grid(const LcView &L, int cap) {
     const int64_t items = L.nblk * L.nseg * L.jb;
@@ -410,8 +472,16 @@ static void lc_sweep(const LcView &L, const double *r, double *z, const int *sto
 }
 
 static void lc_correct(const LcView &L, double *z, const double *xs, const double *v0, double *part0, double *part1,
-                       int grid, const int *stop_col, int col, hipStream_t s) {
+                       int grid, const int *stop_col, int col, hipStream_t s, const double *acc = nullptr) {
     const dim3 g(grid), b(NT);
+    if (acc) {
+        if (L.seg <= 8) hipLaunchKernelGGL(k_linec_correct_acc<7>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col, acc);
+        else if (L.seg <= 16) hipLaunchKernelGGL(k_linec_correct_acc<15>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col, acc);
+        else if (L.seg <= 25) hipLaunchKernelGGL(k_linec_correct_acc<24>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col, acc);
+        else if (L.seg <= 32) hipLaunchKernelGGL(k_linec_correct_acc<31>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col, acc);
+        else hipLaunchKernelGGL(k_linec_correct_acc<0>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col, acc);
+        return;
+    }
     if (L.seg <= 8) hipLaunchKernelGGL(k_linec_correct<7>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col);
     else if (L.seg <= 16) hipLaunchKernelGGL(k_linec_correct<15>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col);
     else if (L.seg <= 25) hipLaunchKernelGGL(k_linec_correct<24>, g, b, 0, s, L, z, xs, v0, part0, part1, stop_col, col);
@@ -440,7 +510,8 @@ hipError_t launch_linec_setup(const int32_t *indptr, const int32_t *indices, con
 }
 
 hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double *z, const double *v0, double *part0,
-                              double *part1, int grid, const int *stop_col, int col, hipStream_t s) {
+                              double *part1, int grid, const int *stop_col, int col, hipStream_t s, const double *zadd) {
+    if (zadd && (phase != 2 || zadd == z)) return hipErrorInvalidValue;
     if (C.n <= 0) {   // a rank without rows: zero partials
         if (phase != 2 || !part0 || grid < 1) return hipSuccess;
         hipError_t e = hipMemsetAsync(part0, 0, (size_t)grid * sizeof(double), s);
@@ -470,7 +541,7 @@ hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double
         }
         return hipGetLastError();
     }
-    lc_correct(L0, z, C.lev[1].x, v0, part0, part1, grid, stop_col, col, s);
+    lc_correct(L0, z, C.lev[1].x, v0, part0, part1, grid, stop_col, col, s, zadd);
     return hipGetLastError();
 }
 

@@ -30,6 +30,7 @@ from ._abi import check, lib
 __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "vlasov_operator", "block_jacobi",
            "gmres", "VlasovParams", "vlasov_params", "rhs_splitmix", "partition_rows",
            "halo_plan", "device_count", "SolveStats", "line_jacobi", "LineJacobi", "line_product", "LineProduct", "line_cyclic", "LineCyclic",
+           "neumann", "Neumann",
            "vlasov_line_period",
            "vlasov_line_directions",
            "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats",
@@ -892,8 +893,83 @@ def line_cyclic(A: CsrOperator, stride: int, period: int, seg: int = 25) -> Line
     return LineCyclic(A, stride, period, seg)
 
 
-_PRECS = (BlockJacobi, LineJacobi, LineProduct, LineCyclic)
-_PRECS_TEXT = "None, vtkrylov.BlockJacobi, vtkrylov.LineJacobi, vtkrylov.LineProduct or vtkrylov.LineCyclic"
+class Neumann:
+    """Neumann-series (polynomial) wrapper around any preconditioner ``M`` of ``A``:
+    ``degree`` steps of preconditioned Richardson from 0, i.e. the degree-(``degree`` - 1) Neumann
+    series of M^-1 A.  More operator work per Krylov vector, fewer Krylov vectors.  SciPy statement::
+
+        def mv(r):
+            z = M(r)
+            for _ in range(degree - 1):
+                z = z + M(r - A @ z)
+            return z
+
+        LinearOperator((n, n), matvec=mv)
+
+    ``vtk_neumann_create``.  1 <= ``degree`` <= 8; ``degree`` 1 is ``M`` itself, bit for bit.  With
+    block Jacobi, line Jacobi and the line product the result equals that composition of the
+    library's own ``A @ x`` and ``M @ x`` bit for bit; with the periodic lines to rounding.
+
+    The wrapper borrows ``M``: it keeps a reference to the Python object, and a wrapper whose base
+    was closed raises VtkError (status ERR_STATE) at its next use.  ``M`` must not be a ``Neumann``
+    and must belong to ``A`` (ValueError).  Whether a degree pays depends on the spectrum of
+    M^-1 A: block Jacobi on the Vlasov operators gains at degree 2 and stalls at degree 3; the line
+    product gains at every degree.  Nothing selects the wrapper by default."""
+
+    def __init__(self, A: CsrOperator, M, degree: int = 2):
+        if not isinstance(M, _PRECS):   # (a Neumann base is the library's VTK_ERR_ARG: ValueError)
+            raise TypeError("vtkrylov.neumann: M must be " + _BASE_PRECS_TEXT)
+        h = C.c_void_p()
+        check(lib().vtk_neumann_create(A.handle, M.handle, int(degree), C.byref(h)), A.ctx.handle)
+        self._h = h
+        self.A = A
+        self.base = M
+        self.degree = int(degree)
+        self.shape = A.shape
+        self.dtype = np.dtype(np.float64)
+        self._epoch = M.values_epoch
+
+    def refresh(self):
+        """Refresh the base from the operator's current values (``vtk_prec_refresh`` on the wrapper
+        refreshes its base; the base's errors pass through)."""
+        try:
+            return _refresh(self)
+        finally:
+            self.base._epoch = self._epoch
+
+    @property
+    def values_epoch(self) -> int:
+        """The base's ``values_epoch``: the wrapper owns no factors."""
+        return self.base.values_epoch
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        """``degree``, ``base`` (the base's kind), ``fused`` (each correction is one SpMV launch
+        with the base in its epilogue: block Jacobi on fused tiles, bs <= 8), ``base_alive``."""
+        o = _abi.NeuInfo()
+        check(lib().vtk_neumann_info(self._h, C.byref(o)), self.A.ctx.handle)
+        return {"degree": int(o.degree), "base": _abi.PREC_KINDS.get(int(o.base_kind)), "fused": bool(o.fused),
+                "base_alive": bool(o.base_alive)}
+
+    matvec = LineJacobi.matvec
+    __matmul__ = LineJacobi.__matmul__
+    close = LineJacobi.close
+    __del__ = LineJacobi.__del__
+
+
+def neumann(A: CsrOperator, M, degree: int = 2) -> Neumann:
+    """``neumann(A, M, degree=2)``: see :class:`Neumann`."""
+    return Neumann(A, M, degree)
+
+
+_BASE_PRECS = (BlockJacobi, LineJacobi, LineProduct, LineCyclic)
+_BASE_PRECS_TEXT = "a vtkrylov.BlockJacobi, vtkrylov.LineJacobi, vtkrylov.LineProduct or vtkrylov.LineCyclic"
+_PRECS = _BASE_PRECS + (Neumann,)
+_PRECS_TEXT = ("None, vtkrylov.BlockJacobi, vtkrylov.LineJacobi, vtkrylov.LineProduct, vtkrylov.LineCyclic "
+               "or vtkrylov.Neumann")
 
 
 @dataclass
@@ -983,7 +1059,7 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     modified Gram-Schmidt sequence (iterative.py:755-759); ``orth="dcgs2"`` forces DCGS2.
 
     ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
-    :class:`BlockJacobi`, a :class:`LineJacobi` or a :class:`LineProduct` built on ``A``; any other preconditioner raises TypeError (no CPU
+    :class:`BlockJacobi`, a :class:`LineJacobi`, a :class:`LineProduct`, a :class:`LineCyclic` or a :class:`Neumann` wrapper built on ``A``; any other preconditioner raises TypeError (no CPU
     fallback).  ``callback`` is not supported (the Arnoldi loop never returns to the host).
     ``restart``/``maxiter``: None = SciPy's defaults (20 / 10 n); explicit values must be
     positive integers (ValueError otherwise).

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "vtk_lineproduct_factors": (C.c_int, [P, C.c_int, P, C.c_int]),
     "vtk_linecyclic_create": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(P)]),
     "vtk_linecyclic_info": (C.c_int, [P, C.c_void_p]),
+    "vtk_neumann_create": (C.c_int, [P, P, C.c_int, C.POINTER(P)]),
+    "vtk_neumann_info": (C.c_int, [P, C.c_void_p]),
     "vtk_prec_apply": (C.c_int, [P, P, P, C.c_int]),
     "vtk_linejacobi_set_compact": (C.c_int, [P, C.c_int]),
     "vtk_linejacobi_get_compact": (C.c_int, [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -163,6 +165,13 @@ class LayoutInfo(C.Structure):
 class LinecInfo(C.Structure):
     _fields_ = [("levels", C.c_int32), ("compact", C.c_int32), ("stride", C.c_int64), ("period", C.c_int64),
                 ("seg", C.c_int64), ("unknowns", C.c_int64 * 32)]
+
+
+class NeuInfo(C.Structure):
+    _fields_ = [("degree", C.c_int32), ("base_kind", C.c_int32), ("fused", C.c_int32), ("base_alive", C.c_int32)]
+
+
+PREC_KINDS = {0: "block_jacobi", 1: "line_jacobi", 2: "line_product", 3: "line_cyclic", 4: "neumann"}
 
 
 class KernelProfile(C.Structure):

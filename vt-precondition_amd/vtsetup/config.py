@@ -83,6 +83,9 @@ class SolverConfig:
     # preconditioner type line_cyclic: the unknowns of one periodic line (optional node; 0 = absent:
     # vtkrylov.vlasov_line_period, Nx)
     line_period: int = 0
+    # preconditioner/neumann_degree (optional node; absent: 1, the preconditioner itself): the type
+    # above wrapped in vtkrylov.neumann of this degree, 1..8
+    neumann_degree: int = 1
 
     @classmethod
     def load(cls, path: str = DEFAULT_XML, **overrides) -> "SolverConfig":
@@ -115,11 +118,16 @@ class SolverConfig:
         cfg.line_stride2 = int(t.get_optional("preconditioner/line_stride2", "0") or 0)
         cfg.line_segment2 = int(t.get_optional("preconditioner/line_segment2", "0") or 0)
         cfg.line_period = int(t.get_optional("preconditioner/line_period", "0") or 0)
+        cfg.neumann_degree = int(t.get_optional("preconditioner/neumann_degree", "1") or 1)
         for k, v in overrides.items():
             if v is not None:
                 setattr(cfg, k, v)
         if cfg.preconditioner not in ("block_jacobi", "line_jacobi", "line_product", "line_cyclic", "none"):
             raise ValueError(f"unknown preconditioner {cfg.preconditioner!r}")
+        if not 1 <= cfg.neumann_degree <= 8:
+            raise ValueError(f"preconditioner/neumann_degree must be in 1..8, got {cfg.neumann_degree}")
+        if cfg.neumann_degree > 1 and cfg.preconditioner == "none":
+            raise ValueError("preconditioner/neumann_degree needs a preconditioner to wrap (type is none)")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")
         if cfg.method not in ("gmres", "bicgstab"):

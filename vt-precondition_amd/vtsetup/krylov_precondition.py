@@ -126,6 +126,11 @@ class KrylovPrecondition:
                                  "(an operator file without a detected x-line structure has neither)")
             self.M = vk.line_cyclic(self.A, stride, period, c.line_segment)
             info.update(line_stride=stride, line_period=period, line_segment=c.line_segment)
+        if c.neumann_degree > 1 and self.M is not None:
+            # the Neumann-series wrapper around the type above (vtkrylov.neumann borrows its base)
+            self.M_base = self.M
+            self.M = vk.neumann(self.A, self.M_base, c.neumann_degree)
+            info["neumann_degree"] = c.neumann_degree
         info["t_setup_s"] = self._max(time.perf_counter() - t)
         self.result["preconditioner"] = info
 
