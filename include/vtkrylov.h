@@ -387,6 +387,45 @@ typedef struct {
     int64_t unknowns[32];
 } vtk_linec_info;
 int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out);
+/* ---- periodic whole lines that span the ranks --------------------------------
+ * The same M as vtk_linecyclic_create for ONE block of lines, n_global == stride * period (the 2D
+ * x-lines, the 4D x-lines), when the row partition cuts the lines: rank p owns a contiguous range
+ * of P_p >= 3 line indices of every line (first row and row count multiples of stride).  `period`
+ * is the global one.  SPIKE over ranks on top of the solver above: each rank factors the open
+ * chunk of its P_p unknowns per line (the first row's coupling a_first to the previous rank's last
+ * row and the last row's c_last to the next rank's first row left out -- both are read from the
+ * CSR's halo columns, summed in stored order from 0.0 like every coefficient), keeps
+ * V_p = M_p^-1 (a_first e_first) and W_p = M_p^-1 (c_last e_last) (16 B per row), and every rank
+ * holds all ranks' spike tips.  An apply solves the chunk, gathers two edge values per line and
+ * rank (ONE all-gather of 16 * stride bytes per rank), solves the ranks' interface system per line
+ * (redundantly on every rank, no pivoting) and corrects x_p = y_p - V_p xi - W_p eta in the last
+ * sweep.  The result is defined to rounding.  With one rank the same path runs with world 1 (it
+ * does not delegate to vtk_linecyclic_create).  At most 16 ranks.
+ * Creation and vtk_prec_refresh are COLLECTIVE, and every rank returns the same class of status:
+ * VTK_ERR_ARG when n_global != stride * period, when a rank's slab is not whole line indices or has
+ * fewer than 3 (decided from an all-gather of the local counts), period < 3, seg < 2, stride < 1;
+ * VTK_ERR_SINGULAR when any rank's chunk has a zero or non-finite pivot (that rank's message names
+ * the row, the others name the rank) or the interface system has one (the message names the line).
+ * Any other failure of one rank in its own part (an allocation, a launch) is gathered too: that rank
+ * returns its error, the others VTK_ERR_PEER, and none is left in a collective; a collective that
+ * itself fails returns at once.
+ * Kind VTK_PREC_LINEC; vtk_linecyclic_info reports the levels of the rank's chunk (unknowns[0] =
+ * P_p) and the global period.  Usable wherever vtk_linecyclic_create's result is -- vtk_prec_apply,
+ * vtk_gmres, vtk_bicgstab, vtk_precond_matvec; every rank must make the same calls -- except as the
+ * base of vtk_neumann_create (VTK_ERR_ARG: out of scope).  The vtk_linejacobi_* and
+ * vtk_lineproduct_* calls refuse it (VTK_ERR_STATE).  vtk_linecyclic_create itself keeps refusing
+ * lines that span ranks.  (additive, ABI 6) */
+int vtk_linecyclic_create_span(vtk_csr *A, int64_t stride, int64_t period, int64_t seg, vtk_prec **out);
+typedef struct {
+    int32_t world, rank;   /* the ranks the lines span, this rank */
+    int32_t spanning;      /* 1 */
+    int32_t reserved;
+    int64_t first_line;    /* the rank's first line index */
+    int64_t local_period;  /* P_p: its line indices */
+    int64_t period;        /* the global period */
+} vtk_linec_span_info;
+/* VTK_ERR_STATE for a preconditioner that does not span (vtk_linecyclic_create's included) */
+int vtk_linecyclic_span_info(vtk_prec *M, vtk_linec_span_info *out);
 /* ---- Neumann-series (polynomial) wrapper around any preconditioner above --------
  * N_k^-1 r:  z_1 = M^-1 r;  z_{i+1} = z_i + M^-1 (r - A z_i), i = 1 .. k-1, with k = degree and
  * M = M_base: the degree-(k-1) Neumann series of M^-1 A, equal to k steps of preconditioned

@@ -555,6 +555,32 @@ int vtk_linecyclic_create(vtk_csr *A, int64_t stride, int64_t period, int64_t se
     });
 }
 
+int vtk_linecyclic_create_span(vtk_csr *A, int64_t stride, int64_t period, int64_t seg, vtk_prec **out) {
+    if (!A || !out) return VTK_ERR_ARG;
+    *out = nullptr;
+    // collective: the arguments are judged inside, from what every rank contributes
+    return make_prec(A, VTK_PREC_LINEC, 0, out, [&](vtk_prec *M) -> int {
+        TRY(linec_span_plan(M, stride, period, seg));
+        return linec_factor(M);
+    });
+}
+
+int vtk_linecyclic_span_info(vtk_prec *M, vtk_linec_span_info *out) {
+    if (!M || !out) return VTK_ERR_ARG;
+    if (M->kind != VTK_PREC_LINEC || !M->linec.sp.on)
+        return fail(M->A->ctx, VTK_ERR_STATE, "vtk_linecyclic_span_info: not a cyclic-line preconditioner that spans the ranks");
+    const LineCSpan &sp = M->linec.sp;
+    vtk_linec_span_info o{};
+    o.world = sp.world;
+    o.rank = sp.rank;
+    o.spanning = 1;
+    o.first_line = sp.i0;
+    o.local_period = M->linec.period;
+    o.period = sp.gperiod;
+    *out = o;
+    return VTK_OK;
+}
+
 int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out) {
     if (!M || !out) return VTK_ERR_ARG;
     if (M->kind != VTK_PREC_LINEC) return fail(M->A->ctx, VTK_ERR_STATE, "vtk_linecyclic_info: not a cyclic-line preconditioner");
@@ -563,7 +589,7 @@ int vtk_linecyclic_info(vtk_prec *M, vtk_linec_info *out) {
     o.levels = C.nlev;
     o.compact = 0;   // the spikes are stored per row
     o.stride = C.stride;
-    o.period = C.period;
+    o.period = C.sp.on ? C.sp.gperiod : C.period;   // (spanning: unknowns[0] is the rank's share of it)
     o.seg = C.seg;
     for (int k = 0; k < C.nlev && k < 32; ++k) o.unknowns[k] = C.lev[k].period;
     *out = o;
@@ -616,6 +642,8 @@ int vtk_neumann_create(vtk_csr *A, vtk_prec *base, int degree, vtk_prec **out) {
     if (!prec_alive(base, 0)) return fail(c, VTK_ERR_STATE, "vtk_neumann_create: the base preconditioner has been destroyed");
     if (base->kind == VTK_PREC_NEUMANN) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: the base is itself a Neumann wrapper (no nesting)");
     if (base->A != A) return fail(c, VTK_ERR_ARG, "vtk_neumann_create: the base preconditioner was built for another operator");
+    if (base->kind == VTK_PREC_LINEC && base->linec.sp.on)
+        return fail(c, VTK_ERR_ARG, "vtk_neumann_create: cyclic lines that span the ranks are not taken as a base");
     TRY(prec_usable(base, "vtk_neumann_create"));
     const int rc = make_prec(A, VTK_PREC_NEUMANN, 0, out, [&](vtk_prec *M) -> int {
         M->base = base;

@@ -128,6 +128,10 @@ inline BjOp bj_op(const vtk_prec *M) {
         o.neumann = true;
         return o;
     }
+    if (M->kind == VTK_PREC_LINEC && M->linec.sp.on) {   // lines that span the ranks: a host routine too (prec_apply)
+        o.span = true;
+        return o;
+    }
     if (M->kind == VTK_PREC_LINEC) {   // periodic whole lines: the three phases (launch_bj_apply)
         o.linec = &M->linec;
         return o;
@@ -184,6 +188,13 @@ inline double linec_reduced_bytes(const LineC &C) {
     return b;
 }
 inline double linec_correct_bytes(const LineC &C) { return 32.0 * (double)C.n + (C.nlev > 1 ? 8.0 * (double)C.lev[1].n : 0.0); }
+// lines that span the ranks: the fused correction also reads V_p and W_p; the rank
+// level between phases 1 and 3 writes two edge values per line (five reads), gathers 16 B per line
+// and rank, and solves the interface system from every rank's four tips and two edge values
+inline double linec_correct_span_bytes(const LineC &C) { return linec_correct_bytes(C) + 16.0 * (double)C.n; }
+inline double linec_span_bytes(const LineC &C) {
+    return (56.0 + (16.0 + 48.0) * (double)C.sp.world + 16.0) * (double)C.stride;
+}
 
 inline double solver_matrix_bytes(const vtk_csr *A);
 inline bool bj_fused(const vtk_prec *M);
@@ -207,6 +218,9 @@ inline double bj_row_bytes(const vtk_prec *M) {
     }
     if (M->kind == VTK_PREC_LINE) return line_row_bytes(M->line);
     // the cyclic lines: the three phases' bytes less the r read and z written that the callers add
+    if (M->kind == VTK_PREC_LINEC && M->linec.sp.on)
+        return (linec_sweep_bytes(M->linec) + linec_reduced_bytes(M->linec) + linec_span_bytes(M->linec) +
+                linec_correct_span_bytes(M->linec)) / (double)std::max<int64_t>(M->linec.n, 1) - 16.0;
     if (M->kind == VTK_PREC_LINEC)
         return (linec_sweep_bytes(M->linec) + linec_reduced_bytes(M->linec) + linec_correct_bytes(M->linec)) /
                    (double)std::max<int64_t>(M->linec.n, 1) - 16.0;
@@ -291,6 +305,27 @@ inline int comm_allgather_i64(vtk_ctx *c, const int64_t *send, int64_t *recv, in
         return VTK_OK;
     }
     NCCLCHK(c, ncclAllGather(send, recv, (size_t)count, ncclInt64, c->comm, c->stream));
+    return VTK_OK;
+}
+
+// every rank contributes `count` doubles (device), receives world*count (device); one rank without
+// a communicator: a device copy
+inline int comm_allgather(vtk_ctx *c, const double *send, double *recv, int64_t count) {
+    if (!c->dist) {
+        HIPCHK(c, hipMemcpyAsync(recv, send, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        return VTK_OK;
+    }
+    if (c->host_comm) {
+        std::vector<double> hs((size_t)count), hr((size_t)count * c->world);
+        HIPCHK(c, hipMemcpyAsync(hs.data(), send, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->hops.allgather(c->hops.user, hs.data(), hr.data(), count * (int64_t)sizeof(double)) != 0)
+            return fail(c, VTK_ERR_STATE, "host allgather hook failed");
+        HIPCHK(c, hipMemcpyAsync(recv, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return VTK_OK;
+    }
+    NCCLCHK(c, ncclAllGather(send, recv, (size_t)count, ncclDouble, c->comm, c->stream));
     return VTK_OK;
 }
 
@@ -490,6 +525,11 @@ int bj_factor(vtk_prec *M);
 int line_factor(vtk_prec *M);
 int line2_factor(vtk_prec *M);
 int linec_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);
+int linec_span_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);   // collective
+// z = M^-1 r of lines that span the ranks (prec_apply's route; the DCGS2 step calls it with
+// prof = true for the per-phase profile classes)
+int linec_span_apply(vtk_ctx *c, vtk_prec *M, const double *r, double *z, const double *v0, double *part0, double *part1,
+                     int grid, const int *stop_col, int col, Vote *vote, bool prof);
 int linec_factor(vtk_prec *M);
 void linec_free(LineC &C);
 int prec_usable(const vtk_prec *M, const char *who);

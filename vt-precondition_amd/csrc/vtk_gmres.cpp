@@ -305,7 +305,9 @@ int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
         Prof pf(c, "spmv", j, P.b_csr + 2 * n8);
         SOFT(launch_spmv(spmv_in(A, &A->tiles, pj), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, stop, j, c->stream));
     }
-    if (P.linec_step) {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
+    if (P.linec_step && s.M->linec.sp.on) {   // lines that span the ranks: the same, with the rank level
+        TRY(linec_span_apply(c, s.M, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, &s.vote, true));
+    } else if (P.linec_step) {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
         const LineC &lc = s.M->linec;
         { Prof pf(c, "linec_sweep", j, linec_sweep_bytes(lc));
           SOFT(launch_linec_phase(lc, 0, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }

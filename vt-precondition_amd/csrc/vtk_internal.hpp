@@ -156,11 +156,29 @@ struct LineCLevel {
     double *x = nullptr;   // levels >= 1: the level's right-hand side, solved in place (n doubles)
     int64_t n = 0, period = 0, seg = 0, nseg = 0;   // unknowns, per line: unknowns, segment length, segments
 };
+// lines that span the ranks (vtk_linecyclic_create_span): the levels above are those
+// of the rank's open chunk of `period` = P_p unknowns per line (one block), the rank level couples
+// the chunks: x_p = y_p - V_p xi - W_p eta with xi the previous rank's last unknown and eta the next
+// rank's first (cyclically)
+constexpr int LINEC_SPAN_MAXW = 16;   // ranks the interface kernel holds in registers
+struct LineCSpan {
+    bool on = false;
+    int world = 1, rank = 0;
+    int64_t gperiod = 0, i0 = 0;   // the global period; the rank's first line index
+    double *vw = nullptr;          // V_p | W_p (n doubles each)
+    int32_t *ecol = nullptr;       // [2][stride] local columns of a_first's / c_last's entries (-1: none)
+    double *tsend = nullptr;       // this rank's V_first | V_last | W_first | W_last (stride each) | flag
+    double *tips = nullptr;        // [world][4 stride + 1] every rank's, gathered at setup
+    double *edge = nullptr;        // this rank's y_first | y_last (stride each), written per apply
+    double *edges = nullptr;       // [world][2 stride] every rank's, gathered per apply
+    double *xe = nullptr;          // xi | eta of this rank (stride each): the interface solve's result
+};
 struct LineC {
     int64_t n = 0, row0 = 0, stride = 1, period = 0, seg = 0, nblk = 0;
     int nlev = 0, serial = 64;
     LineCLevel lev[LINEC_MAXLEV];
     double *minv = nullptr;   // [nblk stride] the last level's reciprocal pivots
+    LineCSpan sp;
 };
 
 // 4D phase-space grid of the Vlasov operators (row = ((ix Ny + iy) Nvx + jvx) Nvy + jvy, x and y
@@ -442,6 +460,9 @@ struct BjOp {
     // the Neumann wrapper: its apply needs the operator and its halo exchange, so
     // it is a host routine (vtk_precond.cpp prec_apply); launch_bj_apply refuses it
     bool neumann = false;
+    // cyclic lines that span the ranks: the apply gathers across ranks, a host
+    // routine as well (prec_apply); launch_bj_apply refuses it
+    bool span = false;
 };
 
 // mm[0] = min, mm[1] = max of idx[0..n) (mm preset to INT_MAX, INT_MIN)
@@ -530,6 +551,20 @@ hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double
                               const double *zadd = nullptr);   // (zadd: phase 2 only)
 hipError_t launch_linec_apply(const LineC &C, const double *r, double *z, const double *v0, double *part0,
                               double *part1, int grid, const int *stop_col, int col, hipStream_t s);
+// the rank level of lines that span the ranks (C.sp).  _rhs: rhs = 0 but a_first in
+// the first local rows (which 0) or c_last in the last (which 1), each the row's stored entries at
+// the column C.sp.ecol names, summed in stored order from 0.0.  _tips: C.sp.tsend from C.sp.vw.
+// _edge: C.sp.edge from the sweep's y in z and level 1's solution (after phases 0 and 1).  _iface:
+// C.sp.xe from C.sp.tips and C.sp.edges, every rank's interface system solved per line (no
+// pivoting); bad (setup; optional): the smallest j whose system has a zero or non-finite pivot.
+// _correct: phase 2 with the rank terms fused in, partials as launch_linec_phase's
+hipError_t launch_linec_span_rhs(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
+                                 const LineC &C, int which, double *rhs, hipStream_t s);
+hipError_t launch_linec_span_tips(const LineC &C, hipStream_t s);
+hipError_t launch_linec_span_edge(const LineC &C, const double *z, const int *stop_col, int col, hipStream_t s);
+hipError_t launch_linec_span_iface(const LineC &C, unsigned long long *bad, const int *stop_col, int col, hipStream_t s);
+hipError_t launch_linec_span_correct(const LineC &C, double *z, const double *v0, double *part0, double *part1,
+                                     int grid, const int *stop_col, int col, hipStream_t s);
 // Neumann wrapper (vtk_neumann.hip): w = z + u, one addition per row, with
 // part0 = sum w^2 and part1 = sum v0 w (optional) over `grid` workgroups; w may alias z or u.
 // launch_neu_add_dc: the same addition with DCGS2 step j's dots behind it (p = V[j], the partials in

@@ -1195,7 +1195,7 @@ __global__ __launch_bounds__(NT) void k_bj_apply_tri(const double *__restrict__ 
 hipError_t launch_bj_apply(const BjOp &bj, int64_t n, const double *r, double *z,
                            const double *v0, double *part0, double *part1, int grid,
                            const int *stop_col, int col, hipStream_t s) {
-    if (bj.neumann) return hipErrorInvalidValue;   // the wrapper applies through vtk::prec_apply (host)
+    if (bj.neumann || bj.span) return hipErrorInvalidValue;   // host routines: they apply through vtk::prec_apply
     if (bj.linec) return launch_linec_apply(*bj.linec, r, z, v0, part0, part1, grid, stop_col, col, s);
     if (bj.line && bj.line2) {
         // line product: t = M1^-1 r into z, then z = M2^-1 (D t) in place

@@ -156,6 +156,10 @@ void linec_free(LineC &C) {
     (void)hipFree(C.minv);
     C.minv = nullptr;
     C.nlev = 0;
+    for (void *p : {(void *)C.sp.vw, (void *)C.sp.ecol, (void *)C.sp.tsend, (void *)C.sp.tips, (void *)C.sp.edge,
+                    (void *)C.sp.edges, (void *)C.sp.xe})
+        (void)hipFree(p);
+    C.sp = LineCSpan{};
 }
 
 // The levels of M->linec and their storage (the arguments are checked by the caller).  Level 0 cuts
@@ -205,7 +209,7 @@ static int64_t linec_row(const LineC &C, int lev, int64_t idx) {
 // Every level's factors and spikes, top down, from the operator's current values (creation and
 // vtk_prec_refresh).  VTK_ERR_SINGULAR: a zero or non-finite pivot at some level (the first such
 // level's smallest row is named).
-int linec_factor(vtk_prec *M) {
+static int linec_factor_local(vtk_prec *M) {
     vtk_csr *A = M->A;
     vtk_ctx *c = A->ctx;
     const LineC &C = M->linec;
@@ -229,10 +233,187 @@ int linec_factor(vtk_prec *M) {
         const int lev = std::min(k, C.nlev - 1);
         const int64_t idx = k < C.nlev ? (int64_t)hb[k]
                                        : ((int64_t)hb[k] / C.stride * C.lev[lev].period + C.lev[lev].period - 1) * C.stride + (int64_t)hb[k] % C.stride;
-        return fail(c, VTK_ERR_SINGULAR, "vtk_linecyclic_create: zero or non-finite pivot at row " + std::to_string(linec_row(C, lev, idx)) +
+        return fail(c, VTK_ERR_SINGULAR, std::string(C.sp.on ? "vtk_linecyclic_create_span" : "vtk_linecyclic_create") +
+                                             ": zero or non-finite pivot at row " + std::to_string(linec_row(C, lev, idx)) +
                                              " (level " + std::to_string(lev) + ")");
     }
     return VTK_OK;
+}
+
+// ---- lines that span the ranks (vtk_linecyclic_create_span) -----------------------
+// The plan: collective.  Every rank contributes (row count, first row, whether its own arguments
+// hold); the decision is made from the gathered table, the same on every rank, after the collective.
+// Then the levels of the rank's open chunk (linec_plan with period P_p, one block) and the rank
+// level's storage.
+static int linec_span_storage(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);
+int linec_span_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    const int W = c->dist ? c->world : 1;
+    if (W > LINEC_SPAN_MAXW)   // (the same on every rank: no collective is entered)
+        return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create_span: at most " + std::to_string(LINEC_SPAN_MAXW) + " ranks");
+    const bool args = stride >= 1 && period >= 3 && seg >= 2 && stride <= INT64_MAX / period && A->n_global == stride * period;
+    std::vector<int64_t> all{A->n_local, A->row_begin, args ? 1 : 0};
+    if (c->dist) {
+        int64_t *mine = reinterpret_cast<int64_t *>(c->d_scal + 128);   // the scalar scratch: no allocation that could fail on one rank only
+        HIPCHK(c, hipMemcpyAsync(mine, all.data(), 3 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        TRY(comm_allgather_i64(c, mine, mine + 3, 3));
+        all.resize(3 * (size_t)W);
+        HIPCHK(c, hipMemcpyAsync(all.data(), mine + 3, all.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    for (int q = 0; q < W; ++q)
+        if (!all[3 * q + 2])
+            return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create_span: stride must be >= 1, period >= 3, seg >= 2 and "
+                                        "n_global == stride * period (one block of lines)");
+    for (int q = 0; q < W; ++q)
+        if (all[3 * q] % stride != 0 || all[3 * q + 1] % stride != 0 || all[3 * q] / stride < 3)
+            return fail(c, VTK_ERR_ARG, "vtk_linecyclic_create_span: rank " + std::to_string(q) + "'s first row and row count "
+                                        "must be multiples of stride, with at least 3 line indices per rank");
+    // the storage: a failure on one rank only (an allocation) must not leave the peers in the tips
+    // gather that follows, so every rank's verdict is gathered first (the scalar scratch again)
+    const int arc = linec_span_storage(M, stride, period, seg);
+    std::vector<int64_t> vr{arc};
+    if (c->dist) {
+        int64_t *mine = reinterpret_cast<int64_t *>(c->d_scal + 128);
+        HIPCHK(c, hipMemcpyAsync(mine, vr.data(), sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        TRY(comm_allgather_i64(c, mine, mine + 1, 1));
+        vr.resize((size_t)W);
+        HIPCHK(c, hipMemcpyAsync(vr.data(), mine + 1, vr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (arc != VTK_OK) return arc;   // (its message stands)
+    for (int q = 0; q < W; ++q)
+        if (vr[q] != VTK_OK)
+            return fail(c, VTK_ERR_PEER, "vtk_linecyclic_create_span: rank " + std::to_string(q) + " could not set up its storage (" +
+                                             vtk_status_string((int)vr[q]) + "); every rank left the creation there");
+    return VTK_OK;
+}
+
+// the levels of the rank's chunk and the rank level's storage (local; linec_span_plan gathers the verdict)
+static int linec_span_storage(vtk_prec *M, int64_t stride, int64_t period, int64_t seg) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    const int W = c->dist ? c->world : 1, me = c->dist ? c->rank : 0;
+    const int64_t Pp = A->n_local / stride;
+    TRY(linec_plan(M, stride, Pp, seg));
+    LineC &C = M->linec;
+    LineCSpan &sp = C.sp;
+    sp.on = true;
+    sp.world = W;
+    sp.rank = me;
+    sp.gperiod = period;
+    sp.i0 = A->row_begin / stride;
+    const size_t S = (size_t)stride;
+    HIPCHK(c, hipMalloc(&sp.vw, 2 * (size_t)C.n * sizeof(double)));
+    HIPCHK(c, hipMalloc(&sp.ecol, 2 * S * sizeof(int32_t)));
+    HIPCHK(c, hipMalloc(&sp.tsend, (4 * S + 1) * sizeof(double)));
+    HIPCHK(c, hipMalloc(&sp.tips, (size_t)W * (4 * S + 1) * sizeof(double)));
+    HIPCHK(c, hipMalloc(&sp.edge, 2 * S * sizeof(double)));
+    HIPCHK(c, hipMalloc(&sp.edges, (size_t)W * 2 * S * sizeof(double)));
+    HIPCHK(c, hipMalloc(&sp.xe, 2 * S * sizeof(double)));
+    // where the CSR keeps the couplings to the neighbour ranks' edge rows: the local column of the
+    // global row (i0 - 1) stride + j (a_first) and (i0 + P_p) stride + j (c_last), modulo the period;
+    // owned columns come first, the halo's follow in ascending global order
+    std::vector<int32_t> ec(2 * S, -1);
+    const int64_t gl = ((sp.i0 - 1 + period) % period) * stride, gr = ((sp.i0 + Pp) % period) * stride;
+    for (int w = 0; w < 2; ++w)
+        for (int64_t j = 0; j < stride; ++j) {
+            const int64_t g = (w ? gr : gl) + j;
+            if (g >= A->row_begin && g < A->row_end) {
+                ec[w * S + j] = (int32_t)(g - A->row_begin);
+            } else {
+                const auto it = std::lower_bound(A->halo_cols.begin(), A->halo_cols.end(), g);
+                if (it != A->halo_cols.end() && *it == g) ec[w * S + j] = (int32_t)(A->n_local + (it - A->halo_cols.begin()));
+            }
+        }
+    HIPCHK(c, hipMemcpy(sp.ecol, ec.data(), ec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return VTK_OK;
+}
+
+// The factors of lines that span the ranks: collective.  The chunk's levels, V_p and W_p by two
+// applications of the local solver, the tips gathered with a flag slot (a rank whose chunk has a
+// zero pivot still joins the gather; every rank then returns VTK_ERR_SINGULAR; after any other
+// failure of one rank the others return VTK_ERR_PEER), the interface
+// system's pivots checked by its own kernel (identical data, the same verdict on every rank).
+static int linec_span_factor(vtk_prec *M) {
+    vtk_csr *A = M->A;
+    vtk_ctx *c = A->ctx;
+    LineC &C = M->linec;
+    const LineCSpan &sp = C.sp;
+    const int64_t S = C.stride, tq = 4 * S + 1;
+    // this rank's part; whatever it returns, the rank joins the gather below with its verdict in
+    // the flag slot (0, 1: a zero pivot, 2: any other failure), so that no peer waits in it alone
+    int rc = linec_factor_local(M);
+    if (rc == VTK_OK)
+        rc = [&]() -> int {
+            DBuf rhs;
+            TRY(dalloc(c, rhs, (size_t)C.n * sizeof(double)));
+            for (int w = 0; w < 2; ++w) {
+                Prof pf(c, "linec_setup", -1, 16.0 * (double)C.n + bj_row_bytes(M) * (double)C.n);
+                HIPCHK(c, launch_linec_span_rhs(A->d_indptr, A->d_indices, A->d_data, A->fp32, C, w, rhs.as<double>(), c->stream));
+                HIPCHK(c, launch_linec_apply(C, rhs.as<double>(), sp.vw + (size_t)w * C.n, nullptr, nullptr, nullptr,
+                                             vector_grid(C.n), nullptr, 0, c->stream));
+            }
+            HIPCHK(c, launch_linec_span_tips(C, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));   // rhs is freed here
+            return VTK_OK;
+        }();
+    const std::string own = rc == VTK_OK ? std::string() : c->err;
+    const double flag = rc == VTK_OK ? 0.0 : rc == VTK_ERR_SINGULAR ? 1.0 : 2.0;
+    HIPCHK(c, hipMemcpyAsync(sp.tsend + 4 * S, &flag, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TRY(comm_allgather(c, sp.tsend, sp.tips, tq));
+    std::vector<double> fl((size_t)sp.world, 0.0);
+    HIPCHK(c, hipMemcpy2DAsync(fl.data(), sizeof(double), sp.tips + 4 * S, (size_t)tq * sizeof(double), sizeof(double),
+                               (size_t)sp.world, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rc != VTK_OK) return fail(c, rc, own);
+    for (int q = 0; q < sp.world; ++q) {
+        if (fl[q] == 1.0)
+            return fail(c, VTK_ERR_SINGULAR, "vtk_linecyclic_create_span: rank " + std::to_string(q) +
+                                                 " met a zero or non-finite pivot in its chunk of the lines");
+        if (fl[q] != 0.0)
+            return fail(c, VTK_ERR_PEER, "vtk_linecyclic_create_span: rank " + std::to_string(q) +
+                                             " failed while factoring its chunk; every rank left there");
+    }
+    // the interface system's pivots (they do not depend on the edge values: zeros)
+    DBuf bad;
+    TRY(dalloc(c, bad, sizeof(unsigned long long)));
+    const unsigned long long none = ~0ull;
+    unsigned long long hb = none;
+    HIPCHK(c, hipMemcpyAsync(bad.p, &none, sizeof(none), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(sp.edges, 0, (size_t)sp.world * 2 * S * sizeof(double), c->stream));
+    HIPCHK(c, launch_linec_span_iface(C, bad.as<unsigned long long>(), nullptr, 0, c->stream));
+    TRY(read_back(c, hb, bad.p));
+    if (hb != none)
+        return fail(c, VTK_ERR_SINGULAR, "vtk_linecyclic_create_span: the interface system of the ranks is singular (zero or "
+                                         "non-finite pivot) on line " + std::to_string(hb));
+    return VTK_OK;
+}
+
+int linec_factor(vtk_prec *M) { return M->linec.sp.on ? linec_span_factor(M) : linec_factor_local(M); }
+
+// z = M^-1 r: phases 1 and 2 of the chunk, the two edge values per line, one gather, the interface
+// system, the fused correction.  Every rank issues the gather at every call (inside a solve also
+// after the stop column, where the kernels return at entry); a failed collective returns at once
+int linec_span_apply(vtk_ctx *c, vtk_prec *M, const double *r, double *z, const double *v0, double *part0, double *part1,
+                     int grid, const int *stop_col, int col, Vote *vote, bool prof) {
+    const LineC &C = M->linec;
+    const auto soft = [&](hipError_t e, const char *what) -> int {
+        if (vote) return vote->launch(e, what);
+        if (e == hipSuccess) return VTK_OK;
+        return fail(c, e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    { Prof pf(c, prof ? "linec_sweep" : nullptr, col, linec_sweep_bytes(C));
+      TRY(soft(launch_linec_phase(C, 0, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, c->stream), "launch_linec_phase(0)")); }
+    { Prof pf(c, prof ? "linec_reduced" : nullptr, col, linec_reduced_bytes(C));
+      TRY(soft(launch_linec_phase(C, 1, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, c->stream), "launch_linec_phase(1)")); }
+    { Prof pf(c, prof ? "linec_span" : nullptr, col, linec_span_bytes(C));
+      TRY(soft(launch_linec_span_edge(C, z, stop_col, col, c->stream), "launch_linec_span_edge"));
+      TRY(comm_allgather(c, C.sp.edge, C.sp.edges, 2 * C.stride));
+      TRY(soft(launch_linec_span_iface(C, nullptr, stop_col, col, c->stream), "launch_linec_span_iface")); }
+    Prof pf(c, prof ? "linec_correct_span" : nullptr, col, linec_correct_span_bytes(C));
+    return soft(launch_linec_span_correct(C, z, v0, part0, part1, grid, stop_col, col, c->stream), "launch_linec_span_correct");
 }
 
 // ---- the registry of live preconditioners (a Neumann wrapper borrows its base) ------------------
@@ -401,6 +582,8 @@ int prec_apply(vtk_ctx *c, vtk_prec *M, int64_t n, const double *r, double *z, c
     *cnt = 0;
     if (M && M->kind == VTK_PREC_NEUMANN)
         return neumann_apply(M, n, r, z, v0, part0, part1, grid, stop_col, col, vote, dots, cnt);
+    if (M && M->kind == VTK_PREC_LINEC && M->linec.sp.on)
+        return linec_span_apply(c, M, r, z, v0, part0, part1, grid, stop_col, col, vote, false);
     return neu_launch(c, vote, launch_bj_apply(bj_op(M), n, r, z, v0, part0, part1, grid, stop_col, col, c->stream),
                       "launch_bj_apply");
 }

@@ -845,12 +845,21 @@ class LineCyclic:
     ``seg`` is only the partition length of the solver (a recursive Schur complement on
     separators); it does not change M.  Vlasov operators: ``stride`` from
     :func:`vlasov_line_stride`, ``period`` from :func:`vlasov_line_period`.  Every cyclic line
-    must lie on one rank (ValueError otherwise)."""
+    must lie on one rank (ValueError otherwise) -- unless ``span=True``.
 
-    def __init__(self, A: CsrOperator, stride: int, period: int, seg: int = 25):
+    ``span=True`` (``vtk_linecyclic_create_span``): the lines may span the ranks.
+    One block of lines only (``n == stride * period``, ``period`` the global one); every rank owns
+    at least 3 whole line indices.  Creation and :meth:`refresh` are then collective -- every rank
+    makes the call and every rank raises alike -- and an apply costs one all-gather of
+    ``16 * stride`` bytes per rank.  With one rank the same path runs with world 1.  Not accepted
+    as the base of :func:`neumann` (ValueError)."""
+
+    def __init__(self, A: CsrOperator, stride: int, period: int, seg: int = 25, span: bool = False):
         h = C.c_void_p()
-        check(lib().vtk_linecyclic_create(A.handle, int(stride), int(period), int(seg), C.byref(h)), A.ctx.handle)
+        create = lib().vtk_linecyclic_create_span if span else lib().vtk_linecyclic_create
+        check(create(A.handle, int(stride), int(period), int(seg), C.byref(h)), A.ctx.handle)
         self._h = h
+        self.span = bool(span)
         self.A = A
         self.stride = int(stride)
         self.period = int(period)
@@ -882,15 +891,25 @@ class LineCyclic:
         return {"levels": int(o.levels), "unknowns": [int(o.unknowns[k]) for k in range(o.levels)],
                 "compact": bool(o.compact), "stride": int(o.stride), "period": int(o.period), "seg": int(o.seg)}
 
+    @property
+    def span_info(self) -> dict:
+        """Of a ``span=True`` preconditioner: ``world``, ``rank``, ``first_line`` (the rank's first
+        line index), ``local_period`` (its line indices, P_p), ``period`` and ``spanning`` (True).
+        VtkError (status ERR_STATE) for one that does not span."""
+        o = _abi.LinecSpanInfo()
+        check(lib().vtk_linecyclic_span_info(self._h, C.byref(o)), self.A.ctx.handle)
+        return {"world": int(o.world), "rank": int(o.rank), "first_line": int(o.first_line),
+                "local_period": int(o.local_period), "period": int(o.period), "spanning": bool(o.spanning)}
+
     matvec = LineJacobi.matvec
     __matmul__ = LineJacobi.__matmul__
     close = LineJacobi.close
     __del__ = LineJacobi.__del__
 
 
-def line_cyclic(A: CsrOperator, stride: int, period: int, seg: int = 25) -> LineCyclic:
-    """``line_cyclic(A, stride, period, seg=25)``: see :class:`LineCyclic`."""
-    return LineCyclic(A, stride, period, seg)
+def line_cyclic(A: CsrOperator, stride: int, period: int, seg: int = 25, span: bool = False) -> LineCyclic:
+    """``line_cyclic(A, stride, period, seg=25, span=False)``: see :class:`LineCyclic`."""
+    return LineCyclic(A, stride, period, seg, span)
 
 
 class Neumann:
@@ -912,7 +931,8 @@ class Neumann:
 
     The wrapper borrows ``M``: it keeps a reference to the Python object, and a wrapper whose base
     was closed raises VtkError (status ERR_STATE) at its next use.  ``M`` must not be a ``Neumann``
-    and must belong to ``A`` (ValueError).  Whether a degree pays depends on the spectrum of
+    and must belong to ``A`` (ValueError); a ``line_cyclic(..., span=True)`` base is refused as
+    well (ValueError).  Whether a degree pays depends on the spectrum of
     M^-1 A: block Jacobi on the Vlasov operators gains at degree 2 and stalls at degree 3; the line
     product gains at every degree.  Nothing selects the wrapper by default."""
 

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "vtk_lineproduct_factors": (C.c_int, [P, C.c_int, P, C.c_int]),
     "vtk_linecyclic_create": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(P)]),
     "vtk_linecyclic_info": (C.c_int, [P, C.c_void_p]),
+    "vtk_linecyclic_create_span": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(P)]),
+    "vtk_linecyclic_span_info": (C.c_int, [P, C.c_void_p]),
     "vtk_neumann_create": (C.c_int, [P, P, C.c_int, C.POINTER(P)]),
     "vtk_neumann_info": (C.c_int, [P, C.c_void_p]),
     "vtk_prec_apply": (C.c_int, [P, P, P, C.c_int]),
@@ -165,6 +167,11 @@ class LayoutInfo(C.Structure):
 class LinecInfo(C.Structure):
     _fields_ = [("levels", C.c_int32), ("compact", C.c_int32), ("stride", C.c_int64), ("period", C.c_int64),
                 ("seg", C.c_int64), ("unknowns", C.c_int64 * 32)]
+
+
+class LinecSpanInfo(C.Structure):
+    _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("spanning", C.c_int32), ("reserved", C.c_int32),
+                ("first_line", C.c_int64), ("local_period", C.c_int64), ("period", C.c_int64)]
 
 
 class NeuInfo(C.Structure):

@@ -83,6 +83,9 @@ class SolverConfig:
     # preconditioner type line_cyclic: the unknowns of one periodic line (optional node; 0 = absent:
     # vtkrylov.vlasov_line_period, Nx)
     line_period: int = 0
+    # preconditioner/line_span (optional node; absent: 0): 1 = the cyclic lines may span the ranks
+    # (vtkrylov.line_cyclic(..., span=True)) -- what run/gpus > 1 needs on the 2D operators
+    line_span: int = 0
     # preconditioner/neumann_degree (optional node; absent: 1, the preconditioner itself): the type
     # above wrapped in vtkrylov.neumann of this degree, 1..8
     neumann_degree: int = 1
@@ -118,6 +121,7 @@ class SolverConfig:
         cfg.line_stride2 = int(t.get_optional("preconditioner/line_stride2", "0") or 0)
         cfg.line_segment2 = int(t.get_optional("preconditioner/line_segment2", "0") or 0)
         cfg.line_period = int(t.get_optional("preconditioner/line_period", "0") or 0)
+        cfg.line_span = int(t.get_optional("preconditioner/line_span", "0") or 0)
         cfg.neumann_degree = int(t.get_optional("preconditioner/neumann_degree", "1") or 1)
         for k, v in overrides.items():
             if v is not None:
@@ -128,6 +132,12 @@ class SolverConfig:
             raise ValueError(f"preconditioner/neumann_degree must be in 1..8, got {cfg.neumann_degree}")
         if cfg.neumann_degree > 1 and cfg.preconditioner == "none":
             raise ValueError("preconditioner/neumann_degree needs a preconditioner to wrap (type is none)")
+        if cfg.line_span not in (0, 1):
+            raise ValueError(f"preconditioner/line_span must be 0 or 1, got {cfg.line_span}")
+        if cfg.line_span and cfg.preconditioner != "line_cyclic":
+            raise ValueError(f"preconditioner/line_span belongs to type line_cyclic, the type is {cfg.preconditioner!r}")
+        if cfg.line_span and cfg.neumann_degree > 1:
+            raise ValueError("preconditioner/line_span: cyclic lines that span the ranks are no base of the Neumann wrapper")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")
         if cfg.method not in ("gmres", "bicgstab"):

@@ -124,8 +124,11 @@ class KrylovPrecondition:
             if stride <= 0 or period <= 0:
                 raise ValueError("line_cyclic needs preconditioner/line_stride and preconditioner/line_period "
                                  "(an operator file without a detected x-line structure has neither)")
-            self.M = vk.line_cyclic(self.A, stride, period, c.line_segment)
+            # preconditioner/line_span: the lines may span the ranks (the 2D operators with run/gpus > 1)
+            self.M = vk.line_cyclic(self.A, stride, period, c.line_segment, span=bool(c.line_span))
             info.update(line_stride=stride, line_period=period, line_segment=c.line_segment)
+            if c.line_span:
+                info["line_span"] = 1
         if c.neumann_degree > 1 and self.M is not None:
             # the Neumann-series wrapper around the type above (vtkrylov.neumann borrows its base)
             self.M_base = self.M
@@ -294,6 +297,8 @@ def test_main(argv=None) -> int:
     ap.add_argument("--report")
     ap.add_argument("--operator-file", help="SciPy save_npz CSR archive to solve")
     ap.add_argument("--preconditioner", choices=["block_jacobi", "line_jacobi", "line_product", "line_cyclic", "none"])
+    ap.add_argument("--line-span", action="store_const", const=1, default=None,
+                    help="line_cyclic: the lines may span the ranks (overrides preconditioner/line_span)")
     ap.add_argument("--orth", choices=["auto", "mgs", "dcgs2"])
     ap.add_argument("--method", choices=["gmres", "bicgstab"], help="solver (overrides solver/method)")
     ap.add_argument("--gpus", type=int, help="ranks (overrides run/gpus)")
@@ -303,7 +308,8 @@ def test_main(argv=None) -> int:
     a = ap.parse_args(argv)
     try:
         cfg = SolverConfig.load(a.xml, config=a.config, report=a.report, operator_file=a.operator_file,
-                                preconditioner=a.preconditioner, orth=a.orth, gpus=a.gpus, comm=a.comm, method=a.method)
+                                preconditioner=a.preconditioner, orth=a.orth, gpus=a.gpus, comm=a.comm, method=a.method,
+                                line_span=a.line_span)
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
             return _rank_main(cfg, a)
         if cfg.gpus > 1:
