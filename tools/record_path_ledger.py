@@ -4,7 +4,8 @@ For every row of the tables below one solve of fixed length runs under the per-k
 profile -- a tolerance no cycle can meet, ``maxiter=2`` restart cycles (BiCGStab: BCG_ITERS
 iterations) -- and one record is kept: per profile class its launch count and its byte total (the
 host's algorithmic figure, a double), and ``band``, ``orth``, ``inner_iters``, ``restarts``,
-``info`` of the solve.  The records of the committed library are tests/golden/path_ledger.json;
+``info`` of the solve (``solver="apply"``: one ``M @ b``; ``"precond_matvec"``: one ``M^-1 A b``; their records
+are the classes alone).  The records of the committed library are tests/golden/path_ledger.json;
 the test replays the tables and compares with ``==``.  A change of the host driver that moves a
 configuration to another path, or changes a launch count or a byte model, shows up as a diff of
 that file and is re-recorded on purpose:
@@ -44,6 +45,7 @@ def _row(id, op, prec=None, solver="gmres", restart=20, tune=None, layout=None, 
 
 
 BJ8, LINE, LINE2 = ("bj", 8), ("line", 8), ("line2", 8, 8)
+LINE64, LINEC, SPAN = ("line", 64), ("linec", 8), ("linec_span", 8)   # seg 64 > 32: no register sweeps (no line_dc kernel)
 # line rows: restart 6 (a line-preconditioned cycle of 20 columns reaches rounding on S2); 4D: 10
 ROWS = [
     # S2 + BJ(8): the band step with the ring start, and each switch that leaves part of it
@@ -85,13 +87,52 @@ ROWS = [
     _row("pmv_s2_bj8", "S2", BJ8, solver="precond_matvec"),
     _row("pmv_s2_line", "S2", LINE, solver="precond_matvec"),
     _row("pmv_s4_bj8_ring64", "S4", BJ8, solver="precond_matvec", tune={"g4_ring": 64}),
+    # the cyclic lines (three phases, then the dots kernel) and line Jacobi through the generic step
+    _row("s2_linec", "S2", LINEC, restart=6, band=0),
+    _row("s2_linec_band_lsv0", "S2", LINEC, restart=6, tune={"band_lsv": 0}, band=0),
+    _row("s2_linec_x0", "S2", LINEC, restart=6, x0=True),
+    _row("s2_line64", "S2", LINE64, restart=6, band=0),
+    # the Neumann wrapper: the fused correction (BJ-fused tiles, bs <= 8), else residual + the base's
+    # launches with the addend; the step's dots behind the last write (neu_dc) where the kind has that form
+    _row("s2_neu2_bj8", "S2", ("neu", 2, BJ8), restart=6, band=0),
+    _row("s2_neu2_bj8_fuse0", "S2", ("neu", 2, BJ8), restart=6, tune={"neu_fuse": 0}, band=0),
+    _row("s2_neu2_bj8_fuse0_dc0", "S2", ("neu", 2, BJ8), restart=6, tune={"neu_fuse": 0, "neu_dc": 0}, band=0),
+    _row("s2_neu2_bj16", "S2", ("neu", 2, ("bj", 16)), restart=6, band=0),
+    _row("s2_neu2_line", "S2", ("neu", 2, LINE), restart=6, band=0),
+    _row("s2_neu2_line_dc0", "S2", ("neu", 2, LINE), restart=6, tune={"neu_dc": 0}, band=0),
+    _row("s2_neu2_line64", "S2", ("neu", 2, LINE64), restart=6, band=0),
+    _row("s2_neu2_line2", "S2", ("neu", 2, LINE2), restart=6, band=0),
+    _row("s2_neu2_line2_dc0", "S2", ("neu", 2, LINE2), restart=6, tune={"neu_dc": 0}, band=0),
+    _row("s2_neu2_linec", "S2", ("neu", 2, LINEC), restart=6, band=0),
+    _row("s2_neu3_line2", "S2", ("neu", 3, LINE2), restart=6, band=0),
+    _row("s2_neu1_bj8", "S2", ("neu", 1, BJ8), restart=6, band=0),
+    _row("s2_neu2_line2_x0", "S2", ("neu", 2, LINE2), restart=6, x0=True),
+    _row("bcg_s2_line2", "S2", LINE2, solver="bicgstab"),
+    _row("bcg_s2_linec", "S2", LINEC, solver="bicgstab"),
+    _row("bcg_s2_neu2_bj8", "S2", ("neu", 2, BJ8), solver="bicgstab"),
+    _row("bcg_s2_neu2_line", "S2", ("neu", 2, LINE), solver="bicgstab"),
+    _row("pmv_s2_line2", "S2", LINE2, solver="precond_matvec"),
+    _row("pmv_s2_linec", "S2", LINEC, solver="precond_matvec"),
+    _row("pmv_s2_neu2_bj8", "S2", ("neu", 2, BJ8), solver="precond_matvec"),
+    # one standalone M @ b per kind
+    _row("app_s2_bj8", "S2", BJ8, solver="apply"),
+    _row("app_s2_bj8_inverse", "S2", BJ8, solver="apply", mode="inverse"),
+    _row("app_s2_line", "S2", LINE, solver="apply"),
+    _row("app_s2_line2", "S2", LINE2, solver="apply"),
+    _row("app_s2_linec", "S2", LINEC, solver="apply"),
+    _row("app_s2_neu3_line2", "S2", ("neu", 3, LINE2), solver="apply"),
 ]
 
 # across ranks (host-staged communicator, the ranks share the GPU): one spawn per group
 RANK_GROUPS = {
     "S2_w2": (2, [_row("s2_bj8_m20", "S2", BJ8, band=1), _row("s2_bj8_m3", "S2", BJ8, restart=3, band=1),
-                  _row("bcg_s2_bj8", "S2", BJ8, solver="bicgstab")]),
-    "S2_w3": (3, [_row("s2_bj8_m20", "S2", BJ8, band=1), _row("s2_bj8_m3", "S2", BJ8, restart=3, band=1)]),
+                  _row("bcg_s2_bj8", "S2", BJ8, solver="bicgstab"),
+                  _row("s2_linec_span", "S2", SPAN, restart=6, band=0),
+                  _row("bcg_s2_linec_span", "S2", SPAN, solver="bicgstab"),
+                  _row("app_s2_linec_span", "S2", SPAN, solver="apply"),
+                  _row("s2_neu2_bj8", "S2", ("neu", 2, BJ8), restart=6, band=0)]),
+    "S2_w3": (3, [_row("s2_bj8_m20", "S2", BJ8, band=1), _row("s2_bj8_m3", "S2", BJ8, restart=3, band=1),
+                  _row("s2_linec_span", "S2", SPAN, restart=6, band=0)]),
     "S4_w2": (2, [_row("s4_bj8_ring64", "S4", BJ8, restart=10, tune={"g4_ring": 64}, band=0),
                   _row("s4_bj8", "S4", BJ8, restart=10, band=0),
                   _row("pmv_s4_bj8_ring64", "S4", BJ8, solver="precond_matvec", tune={"g4_ring": 64})]),
@@ -106,7 +147,12 @@ def _prec(vk, A, p, prec, mode):
         return None
     if prec[0] == "bj":
         return vk.block_jacobi(A, prec[1], mode=mode)
-    sx, sv = vk.vlasov_line_directions(vk.vlasov_params(p.dim, p.shape))[:2]
+    if prec[0] == "neu":   # ("neu", degree, base): the wrapper keeps its base (run_row closes both)
+        return vk.neumann(A, _prec(vk, A, p, prec[2], mode), prec[1])
+    vp = vk.vlasov_params(p.dim, p.shape)
+    if prec[0] in ("linec", "linec_span"):
+        return vk.line_cyclic(A, vk.vlasov_line_stride(vp), vk.vlasov_line_period(vp), prec[1], span=prec[0] == "linec_span")
+    sx, sv = vk.vlasov_line_directions(vp)[:2]
     if prec[0] == "line":
         return vk.line_jacobi(A, sx, prec[1])
     return vk.line_product(A, (sx, prec[1]), (sv, prec[2]))
@@ -142,6 +188,9 @@ def run_row(vk, ctx, row, offsets=None):
                     st = vk.last_bicgstab_stats()
                     rec = dict(iterations=st.iterations, half_step=st.half_step, info=info)
                     bits = dict(x=_sha(x), rnorm=float(st.rnorm).hex())
+                elif row["solver"] == "apply":
+                    z = M @ b
+                    rec, bits = {}, dict(x=_sha(z))
                 else:
                     w = A.precond_matvec(M, b)
                     rec, bits = {}, dict(x=_sha(w))
@@ -151,6 +200,8 @@ def run_row(vk, ctx, row, offsets=None):
     finally:
         if M is not None:
             M.close()
+            if getattr(M, "base", None) is not None:
+                M.base.close()
         A.close()
     return rec, bits
 

@@ -1,6 +1,7 @@
 // vtk_api.cpp -- C-ABI of libvtkrylov.so: argument checks, contexts, the RCCL / host-staged
 // communicator, the tuning switches, and the entry points that hand over to the other host units
-// (vtk_operator.cpp, vtk_precond.cpp, vtk_gmres.cpp, vtk_bicg.cpp; shared pieces: vtk_driver.hpp).
+// (vtk_operator.cpp, vtk_precond.cpp, vtk_apply.cpp, vtk_gmres.cpp, vtk_bicg.cpp; shared pieces:
+// vtk_driver.hpp).
 #include <cctype>
 #include <climits>
 #include <cstdlib>
@@ -687,7 +688,7 @@ int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int 
     double *p0 = c->d_part, *p1 = c->d_part + GMAX;
     if (ring) {
         const double *halo = A->g4.lblk >= 0 ? A->d_halo : nullptr;
-        Prof pf(c, "spmv_bj", -1, solver_matrix_bytes(A) + bj_row_bytes(M) * n + 16.0 * n);
+        Prof pf(c, "spmv_bj", -1, solver_matrix_bytes(A) + prec_row_bytes(M) * n + 16.0 * n);
         if (!halo) {
             TRY(halo_exchange(A, sx.d));
             HIPCHK(c, launch_g4_ring(A->g4, sx.d, nullptr, M->d_tri + M->tri_ld, sw.d, n, A->fp32, c->tune.g4_ring,
@@ -700,13 +701,13 @@ int vtk_precond_matvec(vtk_csr *A, vtk_prec *M, const double *x, double *w, int 
         // dots go to a scratch), the ADVICE r5 pin of the fused kernel against SpMV + sweeps below
         DBuf part;
         TRY(dalloc(c, part, (size_t)DC_NQ * GMAX * sizeof(double)));
-        Prof pf(c, "line_dc", -1, bj_row_bytes(M) * n + 24.0 * n);
+        Prof pf(c, "line_dc", -1, prec_row_bytes(M) * n + 24.0 * n);
         HIPCHK(c, launch_line_spmv_dc(M->line, A->d_lsv, sx.d, sw.d, sx.d, n, 0, part.as<double>(), vector_grid(n),
                                       nullptr, 0, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // part is freed on return
     } else if (!M || bj_fused(M)) {
         TRY(halo_exchange(A, sx.d));
-        Prof pf(c, M ? "spmv_bj" : "spmv_w", -1, solver_matrix_bytes(A) + bj_row_bytes(M) * n + 16.0 * n);
+        Prof pf(c, M ? "spmv_bj" : "spmv_w", -1, solver_matrix_bytes(A) + prec_row_bytes(M) * n + 16.0 * n);
         HIPCHK(c, launch_spmv(lsv_in(spmv_in(A, M ? &M->tiles : &A->tiles, sx.d), A), EPI_PREC, sw.d, nullptr,
                               M ? bj_op(M) : BjOp{}, nullptr, p0, p1, nullptr, 0, c->stream));
     } else {
@@ -778,7 +779,7 @@ int vtk_bjacobi_apply(vtk_prec *M, const double *r, double *z, int kind) {
     TRY(stage_in(c, kind == VTK_PTR_DEVICE ? z : nullptr, n, kind, sz));
     if (M->kind == VTK_PREC_NEUMANN && kind == VTK_PTR_DEVICE && r == z)
         return fail(c, VTK_ERR_ARG, "vtk_prec_apply: a Neumann wrapper cannot apply in place (r and z alias)");
-    { Prof pf(c, prec_cls(M), -1, bj_row_bytes(M) * n + 16.0 * n);
+    { Prof pf(c, prec_cls(M), -1, prec_row_bytes(M) * n + 16.0 * n);
       TRY(prec_apply(c, M, n, sr.d, sz.d, nullptr, nullptr, nullptr, vector_grid(n), nullptr, 0, nullptr)); }
     return stage_out(c, z, sz, n, kind);
 }

@@ -15,14 +15,6 @@ namespace {
 
 static_assert(sizeof(BicgState) <= sizeof(GmresState), "the pinned state mirror holds either solver's record");
 
-// bytes per row of M as the standalone apply and the fused k_bcg_p / k_bcg_s read it: the stored
-// l | m | g of tridiagonal blocks (bj_row_bytes counts the SELL epilogue's m alone), the inverse
-// rows, the line factors
-double bcg_prec_row_bytes(const vtk_prec *M) {
-    if (M && M->kind == VTK_PREC_BJACOBI && bj_op(M).tri) return 24.0;
-    return bj_row_bytes(M);
-}
-
 const Red none{nullptr, 0};
 
 // one solve: its operands (set by run_bicgstab), what follows from them, and the pieces of its schedule
@@ -44,7 +36,7 @@ struct Bicg {
     double *rec = c->d_scal, *my_vote = &c->d_scal[DC_VOTE + 1];
     Vote vote{c, my_vote};   // a launch of the solve that failed: voted across ranks, returned at once on one
     bool fail_pending = c->tune.fail_step >= 0;
-    double n8 = 8.0 * n, b_csr = solver_matrix_bytes(A), b_inv = bcg_prec_row_bytes(M) * n;
+    double n8 = 8.0 * n, b_csr = solver_matrix_bytes(A), b_inv = prec_row_bytes(M, true) * n;   // (tridiagonal blocks: the stored l | m | g)
     BjOp bj = bj_op(M);
     bool fuse = M && c->tune.bcg_fuse && bcg_fusable(bj);
     // work: r (s in place) | rtilde | p | v | t | phat | shat, then the device state

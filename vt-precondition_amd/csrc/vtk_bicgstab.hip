@@ -248,7 +248,7 @@ __global__ __launch_bounds__(NT) void k_bcg_reduce(Red q0, Red q1, Red q2, Red q
 static const double *bcg_mat(const BjOp &bj) { return bj.tri ? bj.tri : bj.inv; }
 
 bool bcg_fusable(const BjOp &bj) {
-    if (bj.line || bj.bs < 1) return false;
+    if (bj.bs < 1) return false;
     if (bj.tri) return bj.bs == 2 || bj.bs == 4 || bj.bs == 8;
     return bj.inv && (bj.bs == 1 || bj.bs == 2 || bj.bs == 4 || bj.bs == 8);
 }

@@ -1,7 +1,7 @@
 // vtk_driver.hpp -- what the host units of libvtkrylov.so share (vtk_api.cpp, vtk_operator.cpp,
-// vtk_precond.cpp, vtk_gmres.cpp, vtk_bicg.cpp): error returns, scope-owned device buffers, the
-// kernel profile, the communicator primitives, the SpMV launch inputs and the byte models of the
-// profile classes; then each unit's entry points.  Host only: never included from a .hip file.
+// vtk_precond.cpp, vtk_apply.cpp, vtk_gmres.cpp, vtk_bicg.cpp): error returns, scope-owned device
+// buffers, the kernel profile, the communicator primitives, the SpMV launch inputs and the operator's
+// byte models; then each unit's entry points.  Host only: never included from a .hip file.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -120,30 +120,12 @@ inline void prof_flush(vtk_ctx *c, int last_col = 1 << 30) {
 }
 
 // the BJ operator the kernels apply (vtk_bj_mode): tridiagonal factors when available and not
-// switched off, else the inverse rows; null M: identity
+// switched off, else the inverse rows; null M, or any other kind: the empty BjOp (identity) -- only
+// block Jacobi has an epilogue form (bj_fused, bj8_tri and bcg_fusable guard its consumers; the other
+// kinds apply through kind_apply, vtk_apply.cpp)
 inline BjOp bj_op(const vtk_prec *M) {
     BjOp o;
-    if (!M) return o;
-    if (M->kind == VTK_PREC_NEUMANN) {   // the wrapper: a host routine (prec_apply), no single launch
-        o.neumann = true;
-        return o;
-    }
-    if (M->kind == VTK_PREC_LINEC && M->linec.sp.on) {   // lines that span the ranks: a host routine too (prec_apply)
-        o.span = true;
-        return o;
-    }
-    if (M->kind == VTK_PREC_LINEC) {   // periodic whole lines: the three phases (launch_bj_apply)
-        o.linec = &M->linec;
-        return o;
-    }
-    if (M->kind == VTK_PREC_LINE || M->kind == VTK_PREC_LINE2) {
-        o.line = &M->line;
-        if (M->kind == VTK_PREC_LINE2) {   // the product: both sweeps (launch_bj_apply)
-            o.line2 = &M->line2;
-            o.diag = M->d_diag;
-        }
-        return o;
-    }
+    if (!M || M->kind != VTK_PREC_BJACOBI) return o;
     o.inv = M->d_inv;
     o.bs = M->bs;
     // a lagged M (not refreshed since its operator's last value update, vtk_prec_refresh) applies
@@ -164,70 +146,12 @@ inline bool bj8_tri(const vtk_prec *M) {
     return M && M->kind == VTK_PREC_BJACOBI && M->bs == 8 && bj_op(M).tri != nullptr;
 }
 
-// profile class of a standalone preconditioner apply (the Neumann wrapper brackets its own
-// launches: neu_resid, neu_corr and the base's class; a null name brackets nothing)
-inline const char *prec_cls(const vtk_prec *M) {
-    if (M && M->kind == VTK_PREC_NEUMANN) return nullptr;
-    if (M && M->kind == VTK_PREC_LINEC) return "linec_apply";   // the three phases of the cyclic lines
-    if (M && M->kind == VTK_PREC_LINE2) return "line2_apply";   // both sweeps of the product
-    return M && M->kind == VTK_PREC_LINE ? "line_apply" : "bj_apply";
-}
-
-// bytes per row of one direction's factors as a sweep reads them: m (compact) or l, m, g
-inline double line_row_bytes(const LineOp &L) { return L.compact ? 8.0 : 24.0; }
-
-// periodic whole lines, algorithmic bytes of the three phases: the level-0 sweep
-// reads r, l, m, g and writes y; the reduced part gathers per separator (r_s, a_s, c_s, two y read,
-// one value written) and runs every reduced level in place (sweep 40 B, correction 32 B per unknown,
-// its own gather; the last level's one lane per line reads its five factor rows); the level-0
-// correction reads y, V, W and the separator values and writes z
-inline double linec_sweep_bytes(const LineC &C) { return 40.0 * (double)C.n; }
-inline double linec_reduced_bytes(const LineC &C) {
-    double b = C.nlev > 1 ? 48.0 * (double)C.lev[1].n : 0.0;
-    for (int k = 1; k < C.nlev; ++k) b += (k + 1 < C.nlev ? 72.0 + 48.0 * (double)C.lev[k + 1].n / (double)std::max<int64_t>(C.lev[k].n, 1) : 88.0) * (double)C.lev[k].n;
-    return b;
-}
-inline double linec_correct_bytes(const LineC &C) { return 32.0 * (double)C.n + (C.nlev > 1 ? 8.0 * (double)C.lev[1].n : 0.0); }
-// lines that span the ranks: the fused correction also reads V_p and W_p; the rank
-// level between phases 1 and 3 writes two edge values per line (five reads), gathers 16 B per line
-// and rank, and solves the interface system from every rank's four tips and two edge values
-inline double linec_correct_span_bytes(const LineC &C) { return linec_correct_bytes(C) + 16.0 * (double)C.n; }
-inline double linec_span_bytes(const LineC &C) {
-    return (56.0 + (16.0 + 48.0) * (double)C.sp.world + 16.0) * (double)C.stride;
-}
-
-inline double solver_matrix_bytes(const vtk_csr *A);
 inline bool bj_fused(const vtk_prec *M);
 
 // the Neumann wrapper's corrections run in one SpMV launch each (EPI_NEU_CORR): a base with
 // BJ-fused tiles, bs <= 8 (tuning neu_fuse 0: the three-launch form, the same bits)
 inline bool neu_fused(const vtk_prec *N) {
     return N && N->kind == VTK_PREC_NEUMANN && N->A->ctx->tune.neu_fuse && bj_fused(N->base) && N->base->bs <= 8;
-}
-
-// algorithmic bytes per row of one BJ application (tridiagonal: the SELL kernels read only m)
-inline double bj_row_bytes(const vtk_prec *M) {
-    if (!M) return 0.0;
-    // the wrapper, less the r read and z written that the callers add: `degree` applications of the
-    // base; per correction the residual (the matrix, z and r read, t written), the base's own t read
-    // and u written, and the addition (z and u read, w written; fused into the base's last write
-    // where the kind allows -- the model keeps the unfused figure)
-    if (M->kind == VTK_PREC_NEUMANN) {
-        const double nn = (double)std::max<int64_t>(M->A->n_local, 1);
-        return M->degree * bj_row_bytes(M->base) + (M->degree - 1) * (solver_matrix_bytes(M->A) / nn + 24.0 + 16.0 + 24.0);
-    }
-    if (M->kind == VTK_PREC_LINE) return line_row_bytes(M->line);
-    // the cyclic lines: the three phases' bytes less the r read and z written that the callers add
-    if (M->kind == VTK_PREC_LINEC && M->linec.sp.on)
-        return (linec_sweep_bytes(M->linec) + linec_reduced_bytes(M->linec) + linec_span_bytes(M->linec) +
-                linec_correct_span_bytes(M->linec)) / (double)std::max<int64_t>(M->linec.n, 1) - 16.0;
-    if (M->kind == VTK_PREC_LINEC)
-        return (linec_sweep_bytes(M->linec) + linec_reduced_bytes(M->linec) + linec_correct_bytes(M->linec)) /
-                   (double)std::max<int64_t>(M->linec.n, 1) - 16.0;
-    // the product: both directions' factors, D, and t = M1^-1 r written and read back
-    if (M->kind == VTK_PREC_LINE2) return line_row_bytes(M->line) + line_row_bytes(M->line2) + 8.0 + 16.0;
-    if (bj_op(M).tri) return M->A->use_sell ? 8.0 : 24.0;
-    return 8.0 * M->bs;
 }
 
 // reducing-kernel grid: a function of the local size on one GPU; GMAX on every rank when
@@ -459,6 +383,14 @@ struct Vote {
     }
 };
 
+// a launch that may be refused: voted when there is a vote (inside a solve), else it fails at once
+inline int soft_launch(vtk_ctx *c, Vote *vote, hipError_t e, const char *what) {
+    if (vote) return vote->launch(e, what);
+    if (e == hipSuccess) return VTK_OK;
+    return fail(c, e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define SOFT_LAUNCH(c, vote, x) TRY(soft_launch((c), (vote), (x), #x))
+
 // the throttle events of a solve (the host runs LOOKAHEAD steps ahead of the device)
 struct EvRing {
     hipEvent_t e[LOOKAHEAD + 1] = {};
@@ -500,39 +432,60 @@ struct UpdateScratch {
 int update_prepare(vtk_csr *A, UpdateScratch &u);
 int update_finish(vtk_csr *A, UpdateScratch &u);
 
-// ---- vtk_precond.cpp: factors from the operator's current values ------------------------------
+// ---- vtk_precond.cpp: factors from the operator's current values, the plans, the registry ------
 // the registry of live preconditioners: a Neumann wrapper borrows its base and finds out here
 // whether the base still exists (vtk_prec_destroy removes it)
 void prec_register(vtk_prec *M);
 void prec_unregister(const vtk_prec *M);
 bool prec_alive(const vtk_prec *M, uint64_t id);
-// DCGS2 step j's operands, for an apply that ends the step's operator (the wrapper's last correction
-// writes the dots partials in launch_dc_dots' layout where its kernels can: *cnt of them, else 0)
+int bj_factor(vtk_prec *M);
+int line_factor(vtk_prec *M);
+int line2_factor(vtk_prec *M);
+int linec_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);
+int linec_span_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);   // collective
+int linec_factor(vtk_prec *M);
+void linec_free(LineC &C);
+int prec_usable(const vtk_prec *M, const char *who);
+
+// ---- vtk_apply.cpp: z = M^-1 r, its profile classes and byte models -----------------------------
+// profile class of a standalone apply (null for the Neumann wrapper, which brackets its own launches:
+// a null name brackets nothing), and its algorithmic bytes per row less the r read and z written.
+// tri_stored: tridiagonal BJ blocks as the stored l | m | g (the standalone apply, the fused BiCGStab
+// kernels) where the default counts the SELL epilogue's m alone
+const char *prec_cls(const vtk_prec *M);
+double prec_row_bytes(const vtk_prec *M, bool tri_stored = false);
+// DCGS2 step j's operands, for an apply that ends the step's operator: where the kind's last kernel
+// has a dots form it writes the dots partials in launch_dc_dots' layout
 struct StepDots {
     const double *V;
     int64_t ld;
     int j;
     double *part;
 };
-// z = M^-1 r for every kind: launch_bj_apply, or the Neumann wrapper's corrections (each with its
-// halo exchange).  part0 = sum z^2, part1 = sum v0 z over `grid` workgroups (optional).  vote: a
-// failed launch is voted (a solve across ranks); null: it returns at once.  r and z must not alias
-// for the wrapper
+// one apply of a non-wrapper kind (kind_apply): z = M^-1 r, or acc + M^-1 r (the kernels' zadd; z must
+// not alias acc).  part0 = sum z^2, part1 = sum v0 z over `grid` workgroups (optional), of the last write
+struct Apply {
+    const double *r;
+    double *z;
+    const double *acc = nullptr;
+    const double *v0 = nullptr;
+    double *part0 = nullptr, *part1 = nullptr;
+    int grid = 0;
+    const int *stop = nullptr;
+    int col = 0;
+    Vote *vote = nullptr;             // a refused launch is voted (a solve); null: it fails at once
+    const StepDots *dots = nullptr;   // asked for: *cnt = grid where the last kernel wrote them, else 0
+    bool prof = false;                // each launch under its own class; false: the caller brackets the apply
+    const char *last_cls = nullptr;   // prof: the last launch's class when not the kind's own ("neu_corr")
+    bool chunk = false;               // lines that span the ranks: the rank's chunk alone (their factorisation)
+};
+// the launches of kind M->kind (null M: the identity), each kind's sequence once
+int kind_apply(vtk_ctx *c, vtk_prec *M, int64_t n, const Apply &a, int *cnt = nullptr);
+// z = M^-1 r for every kind: kind_apply, or the Neumann wrapper's corrections around it (each with its
+// halo exchange; dots and cnt reach the wrapper only).  r and z must not alias for the wrapper
 int prec_apply(vtk_ctx *c, vtk_prec *M, int64_t n, const double *r, double *z, const double *v0, double *part0,
                double *part1, int grid, const int *stop_col, int col, Vote *vote, const StepDots *dots = nullptr,
                int *cnt = nullptr);
-int bj_factor(vtk_prec *M);
-int line_factor(vtk_prec *M);
-int line2_factor(vtk_prec *M);
-int linec_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);
-int linec_span_plan(vtk_prec *M, int64_t stride, int64_t period, int64_t seg);   // collective
-// z = M^-1 r of lines that span the ranks (prec_apply's route; the DCGS2 step calls it with
-// prof = true for the per-phase profile classes)
-int linec_span_apply(vtk_ctx *c, vtk_prec *M, const double *r, double *z, const double *v0, double *part0, double *part1,
-                     int grid, const int *stop_col, int col, Vote *vote, bool prof);
-int linec_factor(vtk_prec *M);
-void linec_free(LineC &C);
-int prec_usable(const vtk_prec *M, const char *who);
 
 // ---- vtk_gmres.cpp / vtk_bicg.cpp: the drivers, and the step launches vtk_precond_matvec shares -
 int run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double rtol, double atol,

@@ -48,7 +48,7 @@ struct Solver {
     hipEvent_t *ev = nullptr;
     int ev_step[LOOKAHEAD + 1], nev = 0, synced = 0;   // throttle(): the recorded events' steps
 };
-#define SOFT(x) TRY(s.vote.launch((x), #x))
+#define SOFT(x) SOFT_LAUNCH(s.c, &s.vote, x)
 
 // ---- path predicates ---------------------------------------------------------------------------
 
@@ -156,7 +156,7 @@ StepPlan step_plan(const Solver &s) {
     P.line_canon = P.line_lsv && A->lsv_canon && c->tune.sell_canon;
     // one rank: the SpMV inside the sweep kernel (y never stored)
     P.line_fuse = P.line_dc && P.line_canon && line_fuse_ok(c, A, M);
-    P.b_inv = bj_row_bytes(M) * n;
+    P.b_inv = prec_row_bytes(M) * n;
     P.b_solver = solver_matrix_bytes(A);
     // line-separable values in the band step (tuning band_lsv 0: the SELL values)
     P.band_lsv = s.band && A->d_lsv && c->tune.band_lsv;
@@ -281,8 +281,9 @@ int step_fused(Solver &s, const StepPlan &P, int j, const double *pj, double b_s
     return VTK_OK;
 }
 
-// line path (line Jacobi, line product): SpMV, then the line sweeps with the step's dots fused
-// behind them
+// line path (line Jacobi, the line product, the cyclic lines): the SpMV in one of its forms, then the
+// kind's launches (kind_apply), each under its own class; the step's dots behind the last sweep where
+// the kind has that form (the product: tuning line2_dc), else in reduce_step's launch_dc_dots (cnt 0)
 int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
     vtk_ctx *c = s.c;
     vtk_csr *A = s.A;
@@ -290,12 +291,13 @@ int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
     const double n8 = P.n8;
     const int *stop = s.stop;
     TRY(halo_exchange(A, pj));
-    const LineOp &lo = s.M->line;
     if (P.line_fuse) {
         Prof pf(c, "line_dc", j, P.b_inv + 8.0 * (double)n + n8 * (j + 2));   // m, D, p, w, V_j
-        SOFT(launch_line_spmv_dc(lo, A->d_lsv, pj, s.w, s.V, s.ld, j, s.dcpart, s.G, stop, j, c->stream));
+        SOFT(launch_line_spmv_dc(s.M->line, A->d_lsv, pj, s.w, s.V, s.ld, j, s.dcpart, s.G, stop, j, c->stream));
         cnt = s.G;
-    } else if (P.line_lsv) {
+        return VTK_OK;
+    }
+    if (P.line_lsv) {
         // line-separable values: 12 B of matrix per row (codes + diagonal)
         Prof pf(c, "spmv_lsv", j, (P.line_canon ? 8.0 * (double)n : P.b_lsv) + 2 * n8);
         SOFT(launch_lsv_spmv(A->sell.d_pk, A->sell.d_dict, A->d_lsv, pj, c->dist ? A->d_halo : nullptr,
@@ -305,34 +307,11 @@ int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
         Prof pf(c, "spmv", j, P.b_csr + 2 * n8);
         SOFT(launch_spmv(spmv_in(A, &A->tiles, pj), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, stop, j, c->stream));
     }
-    if (P.linec_step && s.M->linec.sp.on) {   // lines that span the ranks: the same, with the rank level
-        TRY(linec_span_apply(c, s.M, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, &s.vote, true));
-    } else if (P.linec_step) {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
-        const LineC &lc = s.M->linec;
-        { Prof pf(c, "linec_sweep", j, linec_sweep_bytes(lc));
-          SOFT(launch_linec_phase(lc, 0, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
-        { Prof pf(c, "linec_reduced", j, linec_reduced_bytes(lc));
-          SOFT(launch_linec_phase(lc, 1, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
-        { Prof pf(c, "linec_correct", j, linec_correct_bytes(lc));
-          SOFT(launch_linec_phase(lc, 2, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
-    } else if (P.line2_step) {
-        const LineOp &l2 = s.M->line2;
-        { Prof pf(c, "line_apply", j, line_row_bytes(lo) * n + 2 * n8);   // t = M1^-1 y in place on the SpMV's output
-          SOFT(launch_line_apply(lo, s.tmp, s.tmp, nullptr, nullptr, nullptr, s.G, stop, j, c->stream)); }
-        if (c->tune.line2_dc) {
-            Prof pf(c, "line2_dc", j, (line_row_bytes(l2) + 8.0) * n + n8 * (j + 3));   // t, D, m, w, p, V_j
-            SOFT(launch_line2_dc(l2, s.M->d_diag, s.tmp, s.w, s.V, s.ld, j, pj, s.dcpart, s.G, stop, j, c->stream));
-            cnt = s.G;
-        } else {   // the dots in reduce_step's launch_dc_dots (cnt stays 0)
-            Prof pf(c, "line2_sweep", j, (line_row_bytes(l2) + 8.0) * n + 2 * n8);
-            SOFT(launch_line2_apply(l2, s.M->d_diag, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, stop, j, c->stream));
-        }
-    } else if (!cnt) {
-        Prof pf(c, "line_dc", j, P.b_inv + n8 * (j + 3));   // r, m, w, p, V_j
-        SOFT(launch_line_dc(s.M->line, s.tmp, s.w, s.V, s.ld, j, pj, s.dcpart, s.G, stop, j, c->stream));
-        cnt = s.G;
-    }
-    return VTK_OK;
+    const StepDots dots{s.V, s.ld, j, s.dcpart};
+    Apply a{s.tmp, s.w};
+    a.grid = s.G, a.stop = stop, a.col = j, a.vote = &s.vote, a.prof = true;
+    if (P.line_dc || (P.line2_step && c->tune.line2_dc)) a.dots = &dots;
+    return kind_apply(c, s.M, n, a, &cnt);
 }
 
 // 4D ring step.  Step 0's dots (|p|^2, p.w, |w|^2) in the same sweep; the later steps' dots in
@@ -564,7 +543,7 @@ int residual(Solver &s, const StepPlan &P, Red &rz) {
     Red rr;
     {
         Prof pf(c, P.resid_fused ? "spmv_resid_bj" : "spmv_resid", -1,
-                P.resid_fused ? P.b_solver + bj_row_bytes(M) * n + 3 * P.n8 : P.b_solver + 3 * P.n8);
+                P.resid_fused ? P.b_solver + prec_row_bytes(M) * n + 3 * P.n8 : P.b_solver + 3 * P.n8);
         int g = 0;
         if (P.resid_g4) {
             G4Dots dd;
@@ -723,7 +702,7 @@ int initial_norms(Solver &s, bool &r_is_b) {
     TRY(reduce(c, s.part[0], s.G, rb));
     HIPCHK(c, launch_finalize(rb, &ds->scal[0], 1, c->stream));
     // M b goes to V[0]: with x0 = 0 it is the first cycle's psolve(r) (run_gmres)
-    { Prof pf(c, prec_cls(M), -1, bj_row_bytes(M) * n + 2 * n8);
+    { Prof pf(c, prec_cls(M), -1, prec_row_bytes(M) * n + 2 * n8);
       TRY(prec_apply(c, M, n, s.b, s.V, nullptr, s.part[1], nullptr, s.G, nullptr, 0, nullptr)); }
     TRY(reduce(c, s.part[1], s.G, rmb));
     HIPCHK(c, launch_finalize(rmb, &ds->scal[1], 1, c->stream));
@@ -853,8 +832,7 @@ int vtk::g4_ring_split(vtk_csr *A, const vtk_prec *M, const double *x, double *w
     auto launch = [&](int k, int64_t lo, int64_t hi) -> int {
         const hipError_t e = launch_g4_ring(A->g4, x, A->d_halo, M->d_tri + M->tri_ld, w, n, A->fp32, c->tune.g4_ring, c->tune.g4_gr,
                                             dots ? &dd : nullptr, &g[k], stop, col, c->stream, (int)lo, (int)hi, per, c->tune.g4_fast);
-        if (vote || e == hipSuccess) return vote ? vote->launch(e, "launch_g4_ring") : VTK_OK;
-        return fail(c, e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP, std::string("launch_g4_ring: ") + hipGetErrorString(e));
+        return soft_launch(c, vote, e, "launch_g4_ring");
     };
     if (exch) TRY(halo_exchange_async(A, x));
     {

@@ -445,24 +445,12 @@ LineOp line_plan(int64_t n, int64_t row0, int64_t stride, int64_t seg);
 
 // block-Jacobi operator as the kernels see it: inverse rows f64[nb][bs][bs], or (tri != null)
 // the LU factors of tridiagonal blocks, SoA l | m | g with stride tri_ld (vtk_driver.hpp bj_op, BJ
-// modes).  bs == 0: identity.
+// modes).  bs == 0: identity.  The other kinds have no such form: vtk_apply.cpp launches them
 struct BjOp {
     const double *inv = nullptr;
     const double *tri = nullptr;
     int64_t tri_ld = 0;
     int bs = 0;
-    const LineOp *line = nullptr;   // line Jacobi instead (inv/tri unused)
-    // line product (vtk_lineproduct_create): z = M2^-1 (D (M1^-1 r)) with M1 = line,
-    // M2 = line2 and D = diag (A's diagonal, n doubles)
-    const LineOp *line2 = nullptr;
-    const double *diag = nullptr;
-    const LineC *linec = nullptr;   // periodic whole lines instead (vtk_linecyclic_create)
-    // the Neumann wrapper: its apply needs the operator and its halo exchange, so
-    // it is a host routine (vtk_precond.cpp prec_apply); launch_bj_apply refuses it
-    bool neumann = false;
-    // cyclic lines that span the ranks: the apply gathers across ranks, a host
-    // routine as well (prec_apply); launch_bj_apply refuses it
-    bool span = false;
 };
 
 // mm[0] = min, mm[1] = max of idx[0..n) (mm preset to INT_MAX, INT_MIN)
@@ -543,14 +531,12 @@ hipError_t launch_line2_dc(const LineOp &L, const double *D, const double *t, do
 // that level / of the last level's pivots that is zero or not finite (preset ~0).
 // launch_linec_phase: 0 the level-0 sweep (y into z's interior rows), 1 the separators' right-hand
 // sides and every reduced level, 2 the level-0 correction with part0 = sum z^2, part1 = sum v0 z
-// over grid workgroups.  r and z may alias.  launch_linec_apply: the three in order
+// over grid workgroups.  r and z may alias
 hipError_t launch_linec_setup(const int32_t *indptr, const int32_t *indices, const void *data, int fp32,
                               const LineC &C, int lev, double *co, unsigned long long *bad, hipStream_t s);
 hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double *z, const double *v0, double *part0,
                               double *part1, int grid, const int *stop_col, int col, hipStream_t s,
                               const double *zadd = nullptr);   // (zadd: phase 2 only)
-hipError_t launch_linec_apply(const LineC &C, const double *r, double *z, const double *v0, double *part0,
-                              double *part1, int grid, const int *stop_col, int col, hipStream_t s);
 // the rank level of lines that span the ranks (C.sp).  _rhs: rhs = 0 but a_first in
 // the first local rows (which 0) or c_last in the last (which 1), each the row's stored entries at
 // the column C.sp.ecol names, summed in stored order from 0.0.  _tips: C.sp.tsend from C.sp.vw.

@@ -1195,15 +1195,6 @@ __global__ __launch_bounds__(NT) void k_bj_apply_tri(const double *__restrict__ 
 hipError_t launch_bj_apply(const BjOp &bj, int64_t n, const double *r, double *z,
                            const double *v0, double *part0, double *part1, int grid,
                            const int *stop_col, int col, hipStream_t s) {
-    if (bj.neumann || bj.span) return hipErrorInvalidValue;   // host routines: they apply through vtk::prec_apply
-    if (bj.linec) return launch_linec_apply(*bj.linec, r, z, v0, part0, part1, grid, stop_col, col, s);
-    if (bj.line && bj.line2) {
-        // line product: t = M1^-1 r into z, then z = M2^-1 (D t) in place
-        const hipError_t e = launch_line_apply(*bj.line, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, s);
-        if (e != hipSuccess) return e;
-        return launch_line2_apply(*bj.line2, bj.diag, z, z, v0, part0, part1, grid, stop_col, col, s);
-    }
-    if (bj.line) return launch_line_apply(*bj.line, r, z, v0, part0, part1, grid, stop_col, col, s);
     if (n == 0 && part0 == nullptr) return hipSuccess;
     if (bj.tri) {
         switch (bj.bs) {

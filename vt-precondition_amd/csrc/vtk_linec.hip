@@ -738,15 +738,6 @@ hipError_t launch_linec_phase(const LineC &C, int phase, const double *r, double
     return hipGetLastError();
 }
 
-hipError_t launch_linec_apply(const LineC &C, const double *r, double *z, const double *v0, double *part0,
-                              double *part1, int grid, const int *stop_col, int col, hipStream_t s) {
-    for (int ph = 0; ph < 3; ++ph) {
-        const hipError_t e = launch_linec_phase(C, ph, r, z, v0, part0, part1, grid, stop_col, col, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
 // ---- the rank level's launchers --------------------------------------------------
 static bool lc_span_ok(const LineC &C) {
     return C.sp.on && C.n > 0 && C.nlev >= 2 && C.nblk == 1 && C.sp.world >= 1 && C.sp.world <= LINEC_SPAN_MAXW &&

@@ -1,5 +1,7 @@
-// vtk_precond.cpp -- preconditioner factors from the operator's current values: block Jacobi, line
-// Jacobi, the two-direction line product, the periodic whole lines (vtk_*_create and vtk_prec_refresh call these).
+// vtk_precond.cpp -- preconditioner factors from the operator's current values (block Jacobi, line
+// Jacobi, the two-direction line product, the periodic whole lines and their span over the ranks:
+// vtk_*_create and vtk_prec_refresh call these), the plans of the cyclic lines, and the registry of
+// live preconditioners.  Applying the factors: vtk_apply.cpp.
 #include <climits>
 #include <mutex>
 #include <unordered_map>
@@ -350,10 +352,12 @@ static int linec_span_factor(vtk_prec *M) {
             DBuf rhs;
             TRY(dalloc(c, rhs, (size_t)C.n * sizeof(double)));
             for (int w = 0; w < 2; ++w) {
-                Prof pf(c, "linec_setup", -1, 16.0 * (double)C.n + bj_row_bytes(M) * (double)C.n);
+                Prof pf(c, "linec_setup", -1, 16.0 * (double)C.n + prec_row_bytes(M) * (double)C.n);
                 HIPCHK(c, launch_linec_span_rhs(A->d_indptr, A->d_indices, A->d_data, A->fp32, C, w, rhs.as<double>(), c->stream));
-                HIPCHK(c, launch_linec_apply(C, rhs.as<double>(), sp.vw + (size_t)w * C.n, nullptr, nullptr, nullptr,
-                                             vector_grid(C.n), nullptr, 0, c->stream));
+                Apply ap{rhs.as<double>(), sp.vw + (size_t)w * C.n};
+                ap.grid = vector_grid(C.n);
+                ap.chunk = true;
+                TRY(kind_apply(c, M, C.n, ap));
             }
             HIPCHK(c, launch_linec_span_tips(C, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));   // rhs is freed here
@@ -392,29 +396,6 @@ static int linec_span_factor(vtk_prec *M) {
 }
 
 int linec_factor(vtk_prec *M) { return M->linec.sp.on ? linec_span_factor(M) : linec_factor_local(M); }
-
-// z = M^-1 r: phases 1 and 2 of the chunk, the two edge values per line, one gather, the interface
-// system, the fused correction.  Every rank issues the gather at every call (inside a solve also
-// after the stop column, where the kernels return at entry); a failed collective returns at once
-int linec_span_apply(vtk_ctx *c, vtk_prec *M, const double *r, double *z, const double *v0, double *part0, double *part1,
-                     int grid, const int *stop_col, int col, Vote *vote, bool prof) {
-    const LineC &C = M->linec;
-    const auto soft = [&](hipError_t e, const char *what) -> int {
-        if (vote) return vote->launch(e, what);
-        if (e == hipSuccess) return VTK_OK;
-        return fail(c, e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    { Prof pf(c, prof ? "linec_sweep" : nullptr, col, linec_sweep_bytes(C));
-      TRY(soft(launch_linec_phase(C, 0, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, c->stream), "launch_linec_phase(0)")); }
-    { Prof pf(c, prof ? "linec_reduced" : nullptr, col, linec_reduced_bytes(C));
-      TRY(soft(launch_linec_phase(C, 1, r, z, nullptr, nullptr, nullptr, grid, stop_col, col, c->stream), "launch_linec_phase(1)")); }
-    { Prof pf(c, prof ? "linec_span" : nullptr, col, linec_span_bytes(C));
-      TRY(soft(launch_linec_span_edge(C, z, stop_col, col, c->stream), "launch_linec_span_edge"));
-      TRY(comm_allgather(c, C.sp.edge, C.sp.edges, 2 * C.stride));
-      TRY(soft(launch_linec_span_iface(C, nullptr, stop_col, col, c->stream), "launch_linec_span_iface")); }
-    Prof pf(c, prof ? "linec_correct_span" : nullptr, col, linec_correct_span_bytes(C));
-    return soft(launch_linec_span_correct(C, z, v0, part0, part1, grid, stop_col, col, c->stream), "launch_linec_span_correct");
-}
 
 // ---- the registry of live preconditioners (a Neumann wrapper borrows its base) ------------------
 namespace {
@@ -456,136 +437,6 @@ int prec_usable(const vtk_prec *M, const char *who) {
     if (M->valid) return VTK_OK;
     return fail(M->A->ctx, VTK_ERR_STATE, std::string(who) + ": the preconditioner's last refresh failed (singular); "
                                                                "refresh it from non-singular values first");
-}
-
-// ---- z = M^-1 r for every kind; the Neumann wrapper's corrections ---------------
-namespace {
-
-// a launch of an apply: voted across ranks inside a solve, else returned at once
-int neu_launch(vtk_ctx *c, Vote *vote, hipError_t e, const char *what) {
-    if (vote) return vote->launch(e, what);
-    if (e == hipSuccess) return VTK_OK;
-    return fail(c, e == hipErrorOutOfMemory ? VTK_ERR_NOMEM : VTK_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define NSOFT(x) TRY(neu_launch(c, vote, (x), #x))
-
-// N_k^-1 r: z_1 = M^-1 r, then k - 1 corrections z <- z + M^-1 (r - A z); the last one writes z and
-// the partials (or the step's dots) the caller asked for.  z_i alternate between two of the wrapper's
-// vectors, t = r - A z_i lives in the third
-int neumann_apply(vtk_prec *N, int64_t n, const double *r, double *z, const double *v0, double *part0, double *part1,
-                  int grid, const int *stop, int col, Vote *vote, const StepDots *dots, int *cnt) {
-    vtk_prec *B = N->base;
-    vtk_csr *A = N->A;
-    vtk_ctx *c = A->ctx;
-    const int k = N->degree;
-    const BjOp bop = bj_op(B);
-    const double n8 = 8.0 * (double)n, b_base = bj_row_bytes(B) * (double)n, b_mat = solver_matrix_bytes(A);
-    if (k == 1) {   // the base, bit for bit
-        Prof pf(c, prec_cls(B), col, b_base + 2 * n8);
-        NSOFT(launch_bj_apply(bop, n, r, z, v0, part0, part1, grid, stop, col, c->stream));
-        return VTK_OK;
-    }
-    if (r == z) return fail(c, VTK_ERR_ARG, "Neumann wrapper: the apply's input and output must not alias");
-    const int64_t ld = round_up(std::max<int64_t>(n, 1), 64);
-    double *cur = N->d_neu, *oth = cur + ld, *t = oth + ld;
-    { Prof pf(c, prec_cls(B), col, b_base + 2 * n8);
-      NSOFT(launch_bj_apply(bop, n, r, cur, nullptr, nullptr, nullptr, grid, stop, col, c->stream)); }
-    const bool fuse = neu_fused(N);
-    const double b_fused = (bop.tri ? 24.0 : 8.0 * B->bs) * (double)n;   // the stored l | m | g, or the inverse rows
-    for (int i = 1; i < k; ++i) {
-        const bool last = i == k - 1;
-        double *out = last ? z : oth;
-        const double *lv0 = last ? v0 : nullptr;
-        double *lp0 = last ? part0 : nullptr, *lp1 = last ? part1 : nullptr;
-        const StepDots *ld_ = last ? dots : nullptr;
-        TRY(halo_exchange(A, cur));
-        const SpmvIn in = lsv_in(spmv_in(A, fuse ? &B->tiles : &A->tiles, cur), A);
-        // one launch: w = z + M^-1 (r - A z).  Its partials come per SpMV workgroup: zero-padded up
-        // to the caller's count; a launch with more workgroups than that (operators of fewer than
-        // 512 GMAX rows) leaves them to the dot kernel
-        if (fuse) {
-            const int g = spmv_grid(in);
-            const bool own = lp0 && g <= grid;
-            { Prof pf(c, "neu_corr", col, b_mat + b_fused + 3 * n8);
-              NSOFT(launch_spmv(in, EPI_NEU_CORR, out, r, bop, own ? lv0 : nullptr, own ? lp0 : nullptr, own ? lp1 : nullptr,
-                                stop, col, c->stream)); }
-            if (own && g < grid) {
-                HIPCHK(c, hipMemsetAsync(lp0 + g, 0, (size_t)(grid - g) * sizeof(double), c->stream));
-                if (lp1 && lv0) HIPCHK(c, hipMemsetAsync(lp1 + g, 0, (size_t)(grid - g) * sizeof(double), c->stream));
-            }
-            if (lp0 && !own) {
-                Prof pf(c, "dot", col, (lp1 && lv0 ? 3 : 1) * n8);
-                NSOFT(launch_dot(out, nullptr, n, lp0, grid, c->stream));
-                if (lp1 && lv0) NSOFT(launch_dot(lv0, out, n, lp1, grid, c->stream));
-            }
-        } else {
-            { Prof pf(c, "neu_resid", col, b_mat + 3 * n8);
-              const SpmvIn rin = lsv_in(spmv_in(A, &A->tiles, cur), A);
-              NSOFT(launch_spmv(rin, EPI_NEU_RESID, t, r, BjOp{}, nullptr, nullptr, nullptr, stop, col, c->stream)); }
-            // the step's dots behind the last write, where the kind's kernel has that form
-            const bool dc = ld_ && c->tune.neu_dc && grid <= GMAX && ld_->j <= DC_MAXJ;
-            const double b_dc = dc ? n8 * (ld_->j + 1) : 0.0;   // p and V_j
-            if (B->kind == VTK_PREC_LINE) {
-                const LineOp &L = B->line;
-                Prof pf(c, "neu_corr", col, b_base + 3 * n8 + b_dc);
-                if (dc && L.seg >= 1 && L.seg <= 32) {
-                    NSOFT(launch_line_dc(L, t, out, ld_->V, ld_->ld, ld_->j, ld_->V + (size_t)ld_->j * ld_->ld, ld_->part, grid,
-                                         stop, col, c->stream, cur));
-                    *cnt = grid;
-                } else {
-                    NSOFT(launch_line_apply(L, t, out, lv0, lp0, lp1, grid, stop, col, c->stream, cur));
-                }
-            } else if (B->kind == VTK_PREC_LINE2) {
-                { Prof pf(c, "line_apply", col, line_row_bytes(B->line) * (double)n + 2 * n8);   // t = M1^-1 t in place
-                  NSOFT(launch_line_apply(B->line, t, t, nullptr, nullptr, nullptr, grid, stop, col, c->stream)); }
-                const LineOp &L2 = B->line2;
-                Prof pf(c, "neu_corr", col, (line_row_bytes(L2) + 8.0) * (double)n + 3 * n8 + b_dc);
-                if (dc && L2.seg >= 1 && L2.seg <= 32) {
-                    NSOFT(launch_line2_dc(L2, B->d_diag, t, out, ld_->V, ld_->ld, ld_->j, ld_->V + (size_t)ld_->j * ld_->ld,
-                                          ld_->part, grid, stop, col, c->stream, cur));
-                    *cnt = grid;
-                } else {
-                    NSOFT(launch_line2_apply(L2, B->d_diag, t, out, lv0, lp0, lp1, grid, stop, col, c->stream, cur));
-                }
-            } else if (B->kind == VTK_PREC_LINEC) {
-                const LineC &C = B->linec;
-                { Prof pf(c, "linec_sweep", col, linec_sweep_bytes(C));
-                  NSOFT(launch_linec_phase(C, 0, t, out, nullptr, nullptr, nullptr, grid, stop, col, c->stream)); }
-                { Prof pf(c, "linec_reduced", col, linec_reduced_bytes(C));
-                  NSOFT(launch_linec_phase(C, 1, t, out, nullptr, nullptr, nullptr, grid, stop, col, c->stream)); }
-                Prof pf(c, "neu_corr", col, linec_correct_bytes(C) + n8);
-                NSOFT(launch_linec_phase(C, 2, t, out, lv0, lp0, lp1, grid, stop, col, c->stream, cur));
-            } else {   // block Jacobi off the fused tiles: u = M^-1 t into `out`, then w = z + u in place
-                { Prof pf(c, "bj_apply", col, b_base + 2 * n8);
-                  NSOFT(launch_bj_apply(bop, n, t, out, nullptr, nullptr, nullptr, grid, stop, col, c->stream)); }
-                Prof pf(c, "neu_corr", col, 3 * n8 + b_dc);
-                if (dc) {
-                    NSOFT(launch_neu_add_dc(cur, out, out, n, ld_->V, ld_->ld, ld_->j, ld_->part, grid, stop, col, c->stream));
-                    *cnt = grid;
-                } else {
-                    NSOFT(launch_neu_add(cur, out, out, n, lv0, lp0, lp1, grid, stop, col, c->stream));
-                }
-            }
-        }
-        if (!last) std::swap(cur, oth);
-    }
-    return VTK_OK;
-}
-#undef NSOFT
-
-}  // namespace
-
-int prec_apply(vtk_ctx *c, vtk_prec *M, int64_t n, const double *r, double *z, const double *v0, double *part0,
-               double *part1, int grid, const int *stop_col, int col, Vote *vote, const StepDots *dots, int *cnt) {
-    int none = 0;
-    if (!cnt) cnt = &none;
-    *cnt = 0;
-    if (M && M->kind == VTK_PREC_NEUMANN)
-        return neumann_apply(M, n, r, z, v0, part0, part1, grid, stop_col, col, vote, dots, cnt);
-    if (M && M->kind == VTK_PREC_LINEC && M->linec.sp.on)
-        return linec_span_apply(c, M, r, z, v0, part0, part1, grid, stop_col, col, vote, false);
-    return neu_launch(c, vote, launch_bj_apply(bj_op(M), n, r, z, v0, part0, part1, grid, stop_col, col, c->stream),
-                      "launch_bj_apply");
 }
 
 }  // namespace vtk

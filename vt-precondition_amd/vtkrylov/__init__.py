@@ -547,7 +547,56 @@ def _refresh(M):
     return M
 
 
-class BlockJacobi:
+class _Prec:
+    """What the preconditioner classes share: the handle and its release, the apply, the epoch of
+    the values the factors were computed from."""
+
+    def _adopt(self, h, A: "CsrOperator", epoch: int):
+        self._h = h
+        self.A = A
+        self.shape = A.shape
+        self.dtype = np.dtype(np.float64)
+        self._epoch = epoch
+
+    @property
+    def values_epoch(self) -> int:
+        """``A.values_epoch`` of the values the factors were computed from."""
+        return self._epoch
+
+    @property
+    def handle(self):
+        return self._h
+
+    def matvec(self, r):
+        vr = _Vec(r, self.A.n_local)
+        if vr.kind == _abi.PTR_DEVICE:
+            import torch
+            z = torch.empty_like(vr.obj)
+            check(lib().vtk_prec_apply(self._h, vr.ptr, C.c_void_p(z.data_ptr()), vr.kind), self.A.ctx.handle)
+            self.A.ctx.synchronize()
+            return z
+        z = np.empty(self.A.n_local)
+        check(lib().vtk_prec_apply(self._h, vr.ptr, _np_ptr(z), vr.kind), self.A.ctx.handle)
+        return z
+
+    def __matmul__(self, r):
+        return self.matvec(r)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vtk_prec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        if _exiting[0]:
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BlockJacobi(_Prec):
     """Block-Jacobi preconditioner M = blockdiag(A)^-1 (SciPy: a LinearOperator whose matvec
     applies the bs x bs diagonal-block inverses).  ``vtk_bjacobi_create``.
 
@@ -571,12 +620,8 @@ class BlockJacobi:
             raise ValueError(f"setup must be one of {sorted(self.SETUPS)}")
         h = C.c_void_p()
         check(lib().vtk_bjacobi_create_ex(A.handle, int(bs), self.SETUPS[setup], C.byref(h)), A.ctx.handle)
-        self._h = h
-        self.A = A
+        self._adopt(h, A, A.values_epoch)
         self.bs = bs
-        self.shape = A.shape
-        self.dtype = np.dtype(np.float64)
-        self._epoch = A.values_epoch
         self.set_mode(mode)
 
     def refresh(self):
@@ -609,50 +654,18 @@ class BlockJacobi:
         check(lib().vtk_bjacobi_get_mode(self._h, None, C.byref(t)), self.A.ctx.handle)
         return bool(t.value)
 
-    @property
-    def handle(self):
-        return self._h
-
     def inverse(self) -> np.ndarray:
         nb = (self.A.n_local + self.bs - 1) // self.bs
         inv = np.empty((nb, self.bs, self.bs))
         check(lib().vtk_bjacobi_inverse(self._h, _np_ptr(inv), _abi.PTR_HOST), self.A.ctx.handle)
         return inv
 
-    def matvec(self, r):
-        vr = _Vec(r, self.A.n_local)
-        if vr.kind == _abi.PTR_DEVICE:
-            import torch
-            z = torch.empty_like(vr.obj)
-            check(lib().vtk_bjacobi_apply(self._h, vr.ptr, C.c_void_p(z.data_ptr()), vr.kind), self.A.ctx.handle)
-            self.A.ctx.synchronize()
-            return z
-        z = np.empty(self.A.n_local)
-        check(lib().vtk_bjacobi_apply(self._h, vr.ptr, _np_ptr(z), vr.kind), self.A.ctx.handle)
-        return z
-
-    def __matmul__(self, r):
-        return self.matvec(r)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().vtk_prec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if _exiting[0]:
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def block_jacobi(A: CsrOperator, bs: int = 8, mode: str = "auto", setup: str = "exact") -> BlockJacobi:
     return BlockJacobi(A, bs, mode, setup)
 
 
-class LineJacobi:
+class LineJacobi(_Prec):
     """Line-Jacobi preconditioner (line-implicit x-direction solve):
     M = A's diagonal + the couplings between rows R and R +- ``stride`` within segments of
     ``seg`` consecutive line indices R // stride (and within this rank's rows).  SciPy
@@ -665,13 +678,9 @@ class LineJacobi:
     def __init__(self, A: CsrOperator, stride: int, seg: int = 25):
         h = C.c_void_p()
         check(lib().vtk_linejacobi_create(A.handle, int(stride), int(seg), C.byref(h)), A.ctx.handle)
-        self._h = h
-        self.A = A
+        self._adopt(h, A, A.values_epoch)
         self.stride = int(stride)
         self.seg = int(seg)
-        self.shape = A.shape
-        self.dtype = np.dtype(np.float64)
-        self._epoch = A.values_epoch
 
     def refresh(self):
         """Recompute the Thomas factors from the operator's current values into the storage this
@@ -679,15 +688,6 @@ class LineJacobi:
         apply is dropped or regained accordingly, a ``set_compact(False)`` is kept.  LinAlgError
         on a zero pivot -- unusable (VtkError, status ERR_STATE) until a later refresh succeeds."""
         return _refresh(self)
-
-    @property
-    def values_epoch(self) -> int:
-        """``A.values_epoch`` of the values the factors were computed from."""
-        return self._epoch
-
-    @property
-    def handle(self):
-        return self._h
 
     @property
     def compact(self) -> bool:
@@ -710,34 +710,6 @@ class LineJacobi:
         f = np.empty(3 * self.A.n_local)
         check(lib().vtk_linejacobi_factors(self._h, _np_ptr(f), _abi.PTR_HOST), self.A.ctx.handle)
         return f
-
-    def matvec(self, r):
-        vr = _Vec(r, self.A.n_local)
-        if vr.kind == _abi.PTR_DEVICE:
-            import torch
-            z = torch.empty_like(vr.obj)
-            check(lib().vtk_prec_apply(self._h, vr.ptr, C.c_void_p(z.data_ptr()), vr.kind), self.A.ctx.handle)
-            self.A.ctx.synchronize()
-            return z
-        z = np.empty(self.A.n_local)
-        check(lib().vtk_prec_apply(self._h, vr.ptr, _np_ptr(z), vr.kind), self.A.ctx.handle)
-        return z
-
-    def __matmul__(self, r):
-        return self.matvec(r)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().vtk_prec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if _exiting[0]:
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def line_jacobi(A: CsrOperator, stride: int, seg: int = 25) -> LineJacobi:
@@ -774,7 +746,7 @@ def vlasov_line_directions(params) -> list[int]:
     return [sh[1] * sh[2] * sh[3], sh[2] * sh[3]]
 
 
-class LineProduct:
+class LineProduct(_Prec):
     """Two-direction line preconditioner: the approximate-factorisation product
     M = M1 D^-1 M2 = D + X + Y + X D^-1 Y of two :class:`LineJacobi` matrices of ``A``, given as
     ``(stride, seg)`` pairs, with D = A's diagonal.  SciPy statement:
@@ -787,27 +759,14 @@ class LineProduct:
         (s1, g1), (s2, g2) = dir1, dir2
         h = C.c_void_p()
         check(lib().vtk_lineproduct_create(A.handle, int(s1), int(g1), int(s2), int(g2), C.byref(h)), A.ctx.handle)
-        self._h = h
-        self.A = A
+        self._adopt(h, A, A.values_epoch)
         self.directions = ((int(s1), int(g1)), (int(s2), int(g2)))
-        self.shape = A.shape
-        self.dtype = np.dtype(np.float64)
-        self._epoch = A.values_epoch
 
     def refresh(self):
         """Recompute both directions' Thomas factors and D from the operator's current values and
         re-run the constant-coupling check per direction (``vtk_prec_refresh``).  LinAlgError on a
         zero pivot -- unusable (VtkError, status ERR_STATE) until a later refresh succeeds."""
         return _refresh(self)
-
-    @property
-    def values_epoch(self) -> int:
-        """``A.values_epoch`` of the values the factors were computed from."""
-        return self._epoch
-
-    @property
-    def handle(self):
-        return self._h
 
     def factors(self, which: int) -> np.ndarray:
         """l | m | g of direction ``which`` (0 or 1), 3 * n_local doubles (the oracle's
@@ -824,18 +783,13 @@ class LineProduct:
         check(lib().vtk_lineproduct_factors(self._h, 2, _np_ptr(d), _abi.PTR_HOST), self.A.ctx.handle)
         return d
 
-    matvec = LineJacobi.matvec
-    __matmul__ = LineJacobi.__matmul__
-    close = LineJacobi.close
-    __del__ = LineJacobi.__del__
-
 
 def line_product(A: CsrOperator, dir1, dir2) -> LineProduct:
     """``line_product(A, (stride1, seg1), (stride2, seg2))``: see :class:`LineProduct`."""
     return LineProduct(A, dir1, dir2)
 
 
-class LineCyclic:
+class LineCyclic(_Prec):
     """Periodic whole-line preconditioner: M = A's diagonal + every coupling
     between rows of one line -- R mod ``stride`` and R // (``stride`` * ``period``) equal -- whose
     line indices (R // stride) mod period differ by +-1 modulo ``period``, the wrap included: one
@@ -858,30 +812,17 @@ class LineCyclic:
         h = C.c_void_p()
         create = lib().vtk_linecyclic_create_span if span else lib().vtk_linecyclic_create
         check(create(A.handle, int(stride), int(period), int(seg), C.byref(h)), A.ctx.handle)
-        self._h = h
+        self._adopt(h, A, A.values_epoch)
         self.span = bool(span)
-        self.A = A
         self.stride = int(stride)
         self.period = int(period)
         self.seg = int(seg)
-        self.shape = A.shape
-        self.dtype = np.dtype(np.float64)
-        self._epoch = A.values_epoch
 
     def refresh(self):
         """Refactor every level from the operator's current values (``vtk_prec_refresh``).
         LinAlgError on a zero pivot at any level -- unusable (VtkError, status ERR_STATE) until a
         later refresh succeeds."""
         return _refresh(self)
-
-    @property
-    def values_epoch(self) -> int:
-        """``A.values_epoch`` of the values the factors were computed from."""
-        return self._epoch
-
-    @property
-    def handle(self):
-        return self._h
 
     def info(self) -> dict:
         """``levels`` (the last one is solved by one lane per line), ``unknowns`` per line and
@@ -901,18 +842,13 @@ class LineCyclic:
         return {"world": int(o.world), "rank": int(o.rank), "first_line": int(o.first_line),
                 "local_period": int(o.local_period), "period": int(o.period), "spanning": bool(o.spanning)}
 
-    matvec = LineJacobi.matvec
-    __matmul__ = LineJacobi.__matmul__
-    close = LineJacobi.close
-    __del__ = LineJacobi.__del__
-
 
 def line_cyclic(A: CsrOperator, stride: int, period: int, seg: int = 25, span: bool = False) -> LineCyclic:
     """``line_cyclic(A, stride, period, seg=25, span=False)``: see :class:`LineCyclic`."""
     return LineCyclic(A, stride, period, seg, span)
 
 
-class Neumann:
+class Neumann(_Prec):
     """Neumann-series (polynomial) wrapper around any preconditioner ``M`` of ``A``:
     ``degree`` steps of preconditioned Richardson from 0, i.e. the degree-(``degree`` - 1) Neumann
     series of M^-1 A.  More operator work per Krylov vector, fewer Krylov vectors.  SciPy statement::
@@ -941,13 +877,9 @@ class Neumann:
             raise TypeError("vtkrylov.neumann: M must be " + _BASE_PRECS_TEXT)
         h = C.c_void_p()
         check(lib().vtk_neumann_create(A.handle, M.handle, int(degree), C.byref(h)), A.ctx.handle)
-        self._h = h
-        self.A = A
+        self._adopt(h, A, M.values_epoch)
         self.base = M
         self.degree = int(degree)
-        self.shape = A.shape
-        self.dtype = np.dtype(np.float64)
-        self._epoch = M.values_epoch
 
     def refresh(self):
         """Refresh the base from the operator's current values (``vtk_prec_refresh`` on the wrapper
@@ -962,10 +894,6 @@ class Neumann:
         """The base's ``values_epoch``: the wrapper owns no factors."""
         return self.base.values_epoch
 
-    @property
-    def handle(self):
-        return self._h
-
     def info(self) -> dict:
         """``degree``, ``base`` (the base's kind), ``fused`` (each correction is one SpMV launch
         with the base in its epilogue: block Jacobi on fused tiles, bs <= 8), ``base_alive``."""
@@ -973,11 +901,6 @@ class Neumann:
         check(lib().vtk_neumann_info(self._h, C.byref(o)), self.A.ctx.handle)
         return {"degree": int(o.degree), "base": _abi.PREC_KINDS.get(int(o.base_kind)), "fused": bool(o.fused),
                 "base_alive": bool(o.base_alive)}
-
-    matvec = LineJacobi.matvec
-    __matmul__ = LineJacobi.__matmul__
-    close = LineJacobi.close
-    __del__ = LineJacobi.__del__
 
 
 def neumann(A: CsrOperator, M, degree: int = 2) -> Neumann:
