@@ -6,7 +6,8 @@ tests/test_bicgstab_ranks_host.py checks on the CPU.  Two line-preconditioned ca
 held to equal counts, equal exits and 1e-9.
 
 One spawn runs all the solves of its case; every solve passes maxiter <= 500; the process group has
-a 60 s timeout, so a mismatched collective raises instead of hanging.
+a 60 s timeout, so a mismatched collective raises instead of hanging.  The parity worker also runs
+the truncated solves of tests/test_gpu_bicgstab_steps.py (its ``steps`` plan).
 """
 import functools
 import json
@@ -53,9 +54,11 @@ def _leave(dist):
     dist.destroy_process_group()
 
 
-def _operator(vk, ctx, name, world, layout=None):
+def _operator(vk, ctx, name, world, layout=None, even=True):
+    """even: equal slabs (slab_offsets); else the library's partition in whole lines / planes, for a
+    world that does not divide them."""
     p = twin.CONFIGS[name]
-    offs = slab_offsets(name, world)
+    offs = slab_offsets(name, world) if even else vk.partition_rows(p.n, world, slab_unit(p))
     A = vk.vlasov_operator(vk.vlasov_params(p.dim, p.shape, fp32=p.fp32), ctx=ctx, offsets=offs)
     if layout:
         A.set_layout(layout)
@@ -94,22 +97,29 @@ def _kinds(name):
 
 # ---- 1, 5. parity and the collective sequence of the clean solves ------------------------------
 
-def _parity_worker(rank, world, port, name, layout, outdir):
+def _parity_worker(rank, world, port, name, layout, outdir, steps=None):
+    """steps None: every kind of the case to both tolerances.  steps = ((kind, mode, (k, ...)), ...):
+    the truncated runs rtol = atol = 0, maxiter = k of tests/test_gpu_bicgstab_steps.py, on the
+    library's own partition (any world)."""
     dist, vk, ctx, hc = _join(rank, world, port)
-    A, rb, re_ = _operator(vk, ctx, name, world, layout)
+    A, rb, re_ = _operator(vk, ctx, name, world, layout, even=steps is None)
     b = twin.rhs(twin.CONFIGS[name].n)[rb:re_]
     out, xs = [], {}
-    for kind, mode in _kinds(name):
+    if steps is None:
+        plan = [(kind, mode, [dict(rtol=rtol, maxiter=MAXIT) for rtol in RTOLS]) for kind, mode in _kinds(name)]
+    else:
+        plan = [(kind, mode, [dict(rtol=0.0, atol=0.0, maxiter=k) for k in ks]) for kind, mode, ks in steps]
+    for kind, mode, solves in plan:
         M = _prec(vk, A, name, world, kind, mode)
         if mode != "auto":
             assert M.mode == mode, M.mode
-        for rtol in RTOLS:
+        for kw in solves:
             op0 = len(hc.log)
-            x, info = vk.bicgstab(A, b, rtol=rtol, M=M, maxiter=MAXIT)
+            x, info = vk.bicgstab(A, b, M=M, **kw)
             halo = sum(1 for o in hc.log[op0:] if o[0] == "alltoallv")
             xs[f"x{len(out)}"] = x
-            out.append(dict(kind=kind, mode=mode, rtol=rtol, info=int(info), halo_ops=halo, ops=len(hc.log) - op0,
-                            **_stats(vk.last_bicgstab_stats())))
+            out.append(dict(kind=kind, mode=mode, rtol=kw["rtol"], maxiter=kw["maxiter"], info=int(info), halo_ops=halo,
+                            ops=len(hc.log) - op0, **_stats(vk.last_bicgstab_stats())))
         if M is not None:
             M.close()
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), rb=rb, re=re_, meta=json.dumps(out), commlog=json.dumps(hc.log),
@@ -122,14 +132,14 @@ PARITY = [("S2", 2, "csr"), ("S2", 2, "sell"), ("S2", 4, "csr"), ("S2", 4, "sell
 
 
 @functools.lru_cache(maxsize=None)
-def _parity_run(name, world, layout):
+def _parity_run(name, world, layout, steps=None):
     """One spawn per case, shared by the tests below: (per-rank meta lists, gathered x per solve,
-    per-rank communicator logs)."""
+    per-rank communicator logs).  steps: _parity_worker's."""
     import tempfile
 
     import torch.multiprocessing as mp
     with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_parity_worker, args=(world, _free_port(), name, layout, d), nprocs=world, join=True)
+        mp.spawn(_parity_worker, args=(world, _free_port(), name, layout, d, steps), nprocs=world, join=True)
         z = [np.load(os.path.join(d, f"rank{r}.npz"), allow_pickle=False) for r in range(world)]
         for q in z:
             assert q["errors"].size == 0, q["errors"]
