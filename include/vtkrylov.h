@@ -511,6 +511,44 @@ int vtk_gmres_set_orth(vtk_ctx *ctx, int orth);
  * (vtk_csr_set_line_band); off keeps the separate update pass and fused SpMV step */
 int vtk_gmres_set_band(vtk_ctx *ctx, int on);
 
+/* ---- compressed Krylov basis (additive, ABI 6) ---------------------------
+ * VTK_BASIS_F32: vtk_gmres stores the orthonormal columns of a restart cycle in float32 and
+ * computes in float64 (compressed-basis GMRES).  Off by default; VTK_BASIS_F64 is the solver as
+ * it always was -- the same launches, the same bits, no extra allocation.
+ *
+ * What is rounded, and where.  A cycle keeps the finalised columns v^_0 .. v^_{restart-1} in
+ * float32 and two float64 vectors for the candidates p_j and p_{j+1}.  The cycle start scales
+ * M^-1 r in float64, stores v^_0 = (float) v_0 and applies the operator to the stored value.
+ * The update pass of step j forms v_j = (p_j - V^_j s) / r in float64, stores v^_j = (float) v_j,
+ * and subtracts e_j v^_j -- the stored value widened -- from w: p_{j+1} is float64 and orthogonal
+ * (to rounding) to the columns every later step reads.  The operator is applied to the float64
+ * candidate p_j.  The dots, the projections and the x update x += sum_k y_k v^_k widen the
+ * stored columns and accumulate in float64; a column that enters x before it was stored is
+ * rounded to float32 the same way first.  w, the residual, the Hessenberg matrix, the Givens
+ * rotations and every scalar stay float64, and the true residual is recomputed in float64 at
+ * every restart, so the stopping test is the float64 solver's.
+ *
+ * Results are therefore defined to float32-basis rounding: the stored columns are orthonormal to
+ * about 6e-8 instead of 1e-16, x and the iteration count agree with the float64 basis to the
+ * solver's tolerance, not bit for bit, and a cycle that alone reduces the residual by about 2^24
+ * or more pays an extra cycle.  Runs are deterministic.
+ *
+ * The option runs on the DCGS2 sequence with the separate dots and update passes: the line-band
+ * step is not taken (vtk_stats.band = 0) and no operator step fuses the dots of a step that reads
+ * stored columns.  With the MGS sequence (VTK_ORTH_MGS, or VTK_ORTH_AUTO with restart > 32) vtk_gmres
+ * returns VTK_ERR_ARG: select DCGS2.  Across ranks every rank must make the same choice; otherwise
+ * every rank returns VTK_ERR_ARG.  The capture hook returns the float32 columns widened
+ * (VTK_CAP_V), with the candidate still open at cycle end in its column; final_cols keeps its
+ * DCGS2 rule. */
+typedef enum { VTK_BASIS_F64 = 0, VTK_BASIS_F32 = 1 } vtk_basis;
+int vtk_gmres_set_basis(vtk_ctx *ctx, int basis);   /* an unknown value: VTK_ERR_ARG */
+typedef struct {
+    int32_t requested, used;   /* vtk_basis: set on ctx; used by the last vtk_gmres on ctx       */
+    int64_t basis_bytes;       /* that solve's basis: the stored columns and candidate vectors   */
+    int64_t workspace_bytes;   /* that solve's whole workspace (basis included)                  */
+} vtk_basis_info;
+int vtk_gmres_basis_info(vtk_ctx *ctx, vtk_basis_info *out);
+
 /* ---- capture of one restart cycle (a TEST HOOK: off by default, not part of the integration
  * surface; additive, ABI 6) -----------------------------------------------------------------
  * The solver's workspace after a solve does not show a cycle's Arnoldi factorisation: the

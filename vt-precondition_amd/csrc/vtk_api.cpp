@@ -938,6 +938,20 @@ int vtk_gmres_set_orth(vtk_ctx *c, int orth) {
     return VTK_OK;
 }
 
+int vtk_gmres_set_basis(vtk_ctx *c, int basis) {
+    if (!c || (basis != VTK_BASIS_F64 && basis != VTK_BASIS_F32))
+        return fail(c, VTK_ERR_ARG, "vtk_gmres_set_basis: unknown basis storage (VTK_BASIS_F64 or VTK_BASIS_F32)");
+    c->basis = basis;
+    return VTK_OK;
+}
+
+int vtk_gmres_basis_info(vtk_ctx *c, vtk_basis_info *out) {
+    if (!c || !out) return fail(c, VTK_ERR_ARG, "vtk_gmres_basis_info: NULL argument");
+    *out = c->basis_info;
+    out->requested = c->basis;
+    return VTK_OK;
+}
+
 int vtk_gmres_capture(vtk_ctx *c, int cycle) {
     if (!c || cycle < -2) return fail(c, VTK_ERR_ARG, "vtk_gmres_capture: cycle must be >= 0, -1 (off) or -2 (every cycle)");
     c->cap_cycle = cycle;

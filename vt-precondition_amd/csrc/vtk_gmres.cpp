@@ -28,6 +28,13 @@ struct Solver {
     bool dc = false;
     double *Hraw = nullptr, *dcpart = nullptr;   // DCGS2
     DcCoef *cf = nullptr;
+    // compressed basis (vtk_gmres_set_basis): the finalised columns in float32, the
+    // candidates p_j in pc[j % 2]; V is null.  start(): where the cycle's start direction M^-1 r is written
+    bool cb = false;
+    float *Vc = nullptr;
+    double *pc[2] = {};
+    double *cand(int j) const { return cb ? pc[j & 1] : V + (size_t)j * ld; }
+    double *start() const { return cand(0); }
     // line-band DCGS2 step (k_band_step): grid, parts per line; w rotates over s.w, s.tmp, w3
     // (step j's w in the buffer j % 3: the band step reads w_{j-1} and w_j, writes w_{j+1})
     bool band = false;
@@ -136,7 +143,9 @@ StepPlan step_plan(const Solver &s) {
     // the ring step also across ranks: interior groups while the halo planes
     // are in flight, the boundary planes' groups once they have landed
     P.ring4 = P.g4_ring && A->use_sell && A->sell.uniform_w > 8 && !P.g4_fused;
-    P.fused = bj_fused(M) && M->bs <= 8 && !P.wide9 && !P.ring4;
+    // (the compressed basis keeps the dots of steps that read stored columns out of the operator step:
+    // SpMV + BJ without dots, then the compressed dots kernel)
+    P.fused = bj_fused(M) && M->bs <= 8 && !P.wide9 && !P.ring4 && !s.cb;
     P.ring0 = P.fused && s.band && cyc_ring_ok(c, A, M, true);
     // line Jacobi with segments <= 32 (register sweeps): dots fused into the sweep kernel
     P.line_dc = M && M->kind == VTK_PREC_LINE && M->line.seg >= 1 && M->line.seg <= 32 && s.G <= GMAX;
@@ -155,7 +164,7 @@ StepPlan step_plan(const Solver &s) {
     // canonical rows: the diagonal only (tuning sell_canon 0: the codes too; A/B)
     P.line_canon = P.line_lsv && A->lsv_canon && c->tune.sell_canon;
     // one rank: the SpMV inside the sweep kernel (y never stored)
-    P.line_fuse = P.line_dc && P.line_canon && line_fuse_ok(c, A, M);
+    P.line_fuse = P.line_dc && P.line_canon && line_fuse_ok(c, A, M) && !s.cb;
     P.b_inv = prec_row_bytes(M) * n;
     P.b_solver = solver_matrix_bytes(A);
     // line-separable values in the band step (tuning band_lsv 0: the SELL values)
@@ -310,7 +319,7 @@ int step_line(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt) {
     const StepDots dots{s.V, s.ld, j, s.dcpart};
     Apply a{s.tmp, s.w};
     a.grid = s.G, a.stop = stop, a.col = j, a.vote = &s.vote, a.prof = true;
-    if (P.line_dc || (P.line2_step && c->tune.line2_dc)) a.dots = &dots;
+    if (!s.cb && (P.line_dc || (P.line2_step && c->tune.line2_dc))) a.dots = &dots;
     return kind_apply(c, s.M, n, a, &cnt);
 }
 
@@ -346,7 +355,7 @@ int step_neumann(Solver &s, const StepPlan &P, int j, const double *pj, int &cnt
     { Prof pf(c, "spmv", j, P.b_solver + 2 * P.n8);
       SOFT(launch_spmv(lsv_in(spmv_in(A, &A->tiles, pj), A), EPI_PLAIN, s.tmp, nullptr, BjOp{}, nullptr, nullptr, nullptr, s.stop, j, c->stream)); }
     const StepDots dots{s.V, s.ld, j, s.dcpart};
-    return prec_apply(c, s.M, s.n, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, s.stop, j, &s.vote, &dots, &cnt);
+    return prec_apply(c, s.M, s.n, s.tmp, s.w, nullptr, nullptr, nullptr, s.G, s.stop, j, &s.vote, s.cb ? nullptr : &dots, &cnt);
 }
 
 // the form step j takes (the plan's order of precedence)
@@ -376,7 +385,11 @@ int operator_step(Solver &s, const StepPlan &P, int j, double *pj, int &cnt) {
 // has finished: every RCCL operation of the communicator runs in one order, on every rank
 int reduce_step(Solver &s, int j, const double *w, int tag, int cnt, hipEvent_t ev_ar = nullptr) {
     vtk_ctx *c = s.c;
-    if (cnt == 0) {
+    if (cnt == 0 && s.cb) {
+        Prof pf(c, "cb_dots", tag, (double)s.n * (4.0 * j + (w ? 16.0 : 8.0)));
+        SOFT(launch_cb_dots(s.Vc, s.ld, j, s.cand(j), w, s.n, s.dcpart, s.G, s.stop, tag, c->stream));
+        cnt = s.G;
+    } else if (cnt == 0) {
         Prof pf(c, "dc_dots", tag, 8.0 * s.n * (j + (w ? 2 : 1)));
         SOFT(launch_dc_dots(s.V, s.ld, j, w, s.n, s.dcpart, s.G, s.stop, tag, c->stream));
         cnt = s.G;
@@ -393,7 +406,7 @@ int reduce_step(Solver &s, int j, const double *w, int tag, int cnt, hipEvent_t 
         part = nullptr;
     }
     Prof pf(c, "dc_scalar", tag, 0.0);
-    HIPCHK(c, launch_dc_scalar(part, cnt, c->d_scal, j, s.m, w == nullptr, s.Hraw, s.H, s.S, s.giv, s.cf, c->d_state, c->d_stop, c->stream));
+    HIPCHK(c, launch_dc_scalar(part, cnt, c->d_scal, j, s.m, w == nullptr, s.Hraw, s.H, s.S, s.giv, s.cf, c->d_state, c->d_stop, c->stream, s.cb ? 1 : 0));
     return VTK_OK;
 }
 
@@ -473,7 +486,7 @@ int dcgs2_cycle(Solver &s, const StepPlan &P) {
     bool broke = false;
     s.nev = s.synced = 0;
     for (int j = 0; j < m && !broke; ++j) {
-        double *pj = s.V + (size_t)j * s.ld;
+        double *pj = s.cand(j);
         double *w_cur = s.band ? s.wbuf(j) : s.w;
         int cnt = 0;
         TRY(operator_step(s, P, j, pj, cnt));
@@ -486,6 +499,9 @@ int dcgs2_cycle(Solver &s, const StepPlan &P) {
         if (ghost_x) TRY(ghost_exchange(s, j, w_cur));
         if (s.band && j <= m - 2) {
             TRY(band_step(s, P, j));
+        } else if (s.cb) {   // p_j, w, the j stored columns; v^_j and p_{j+1} written
+            Prof pf(c, "cb_update", j, (double)s.n * (4.0 * j + 28.0));
+            SOFT(launch_cb_update(s.Vc, s.ld, j, pj, w_cur, s.cand(j + 1), s.n, s.cf, s.G, c->d_state, s.x, s.H, s.S, m, c->stream));
         } else {
             Prof pf(c, "dc_update", j, P.n8 * (j + 4));
             SOFT(launch_dc_update(s.V, s.ld, j, w_cur, s.n, s.cf, s.G, c->d_state, s.x, s.H, s.S, m, P.fused ? 0 : 1, c->stream));
@@ -548,16 +564,16 @@ int residual(Solver &s, const StepPlan &P, Red &rz) {
         if (P.resid_g4) {
             G4Dots dd;
             dd.mode = 3, dd.b = b, dd.p0 = prr, dd.p1 = prz;
-            SOFT(launch_g4_ring(A->g4, x, A->g4.lblk >= 0 ? A->d_halo : nullptr, M->d_tri + M->tri_ld, s.V, n, A->fp32,
+            SOFT(launch_g4_ring(A->g4, x, A->g4.lblk >= 0 ? A->d_halo : nullptr, M->d_tri + M->tri_ld, s.start(), n, A->fp32,
                                 c->tune.g4_ring, c->tune.g4_gr, &dd, &g, nullptr, 0, c->stream, 0, -1, 0, c->tune.g4_fast));
         } else if (P.resid_ring) {
             SOFT(launch_lsv_ring_epi(P.resid_fused ? EPI_RESID_PREC : EPI_RESID, A->d_lsv, x, b,
-                                     P.resid_fused ? M->d_tri + M->tri_ld : nullptr, P.resid_fused ? s.V : s.r, prr, prz,
+                                     P.resid_fused ? M->d_tri + M->tri_ld : nullptr, P.resid_fused ? s.start() : s.r, prr, prz,
                                      nullptr, n, (int)A->band_L, c->tune.cyc_ring, nullptr, 0, &g, c->stream,
                                      A->band_ghost ? A->d_halo : nullptr, A->band_lblk, A->band_xord));
         } else if (P.resid_fused) {
             const SpmvIn in = lsv_in(spmv_in(A, P.rtiles, x), A);
-            SOFT(launch_spmv(in, EPI_RESID_PREC, s.V, b, bj_op(M), nullptr, prr, prz, nullptr, 0, c->stream));
+            SOFT(launch_spmv(in, EPI_RESID_PREC, s.start(), b, bj_op(M), nullptr, prr, prz, nullptr, 0, c->stream));
             g = spmv_grid(in);
         } else {
             const SpmvIn in = lsv_in(spmv_in(A, &A->tiles, x), A);
@@ -586,7 +602,7 @@ int grow(vtk_ctx *c, T *&p, size_t &bytes, size_t need) {
     return VTK_OK;
 }
 
-// workspace: V[(m+1) x ld] | w | tmp | r | H[m x (m+1)] | S[m+1] | giv[2m]  (doubles), then the
+// workspace: V[(m+1) x ld] (compressed basis: Vc[(m+1) x ld] floats | p_even | p_odd) | w | tmp | r | H[m x (m+1)] | S[m+1] | giv[2m]  (doubles), then the
 // DCGS2 pieces, then (band) the third w buffer, the ghost lines [2][m+2][L] and the send / receive
 // pieces
 int layout_workspace(Solver &s) {
@@ -597,10 +613,20 @@ int layout_workspace(Solver &s) {
     const size_t nghost = (s.band && A->band_ghost)
                               ? (size_t)2 * (m + 2) * A->band_L + 4 * (size_t)BAND_GHOST_VECS * A->band_L : 0;
     const size_t nedge = s.band ? (size_t)s.ld + nghost : 0;
-    const size_t nd = (size_t)(m + 1) * s.ld + 3 * (size_t)s.ld + (size_t)m * (m + 1) + (m + 1) + 2 * m + 64 + ndc + nedge + 16;
+    // the basis: (m + 1) ld doubles, or (compressed) (m + 1) ld floats and the two candidate vectors
+    const size_t nbasis = s.cb ? (size_t)(m + 1) * s.ld / 2 + 2 * (size_t)s.ld : (size_t)(m + 1) * s.ld;
+    const size_t nd = nbasis + 3 * (size_t)s.ld + (size_t)m * (m + 1) + (m + 1) + 2 * m + 64 + ndc + nedge + 16;
     TRY(grow(c, c->ws, c->ws_bytes, nd * sizeof(double)));
     double *wp = static_cast<double *>(c->ws);
-    s.V = wp; wp += (size_t)(m + 1) * s.ld;
+    if (s.cb) {   // (ld is a multiple of 64: every column and both candidates stay 64-B aligned)
+        s.Vc = reinterpret_cast<float *>(wp); wp += (size_t)(m + 1) * s.ld / 2;
+        s.pc[0] = wp; wp += s.ld;
+        s.pc[1] = wp; wp += s.ld;
+    } else {
+        s.V = wp; wp += (size_t)(m + 1) * s.ld;
+    }
+    c->basis_info = vtk_basis_info{c->basis, s.cb ? VTK_BASIS_F32 : VTK_BASIS_F64, (int64_t)(nbasis * sizeof(double)),
+                                   (int64_t)(nd * sizeof(double))};
     s.w = wp; wp += s.ld;
     s.tmp = wp; wp += s.ld;
     s.r = wp; wp += s.ld;
@@ -650,7 +676,8 @@ struct Capture {
     // after the x update, before residual() writes the next v0 direction into V[0]
     int copy_cycle(const Solver &s) const {
         vtk_ctx *c = s.c;
-        HIPCHK(c, hipMemcpyAsync(V, s.V, (size_t)(s.m + 1) * s.ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (s.cb) HIPCHK(c, launch_cb_capture(s.Vc, s.ld, s.m, s.pc[0], s.pc[1], c->d_state, V, c->stream));
+        else HIPCHK(c, hipMemcpyAsync(V, s.V, (size_t)(s.m + 1) * s.ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(H, s.H, hsg * sizeof(double), hipMemcpyDeviceToDevice, c->stream));   // H | S | giv
         if (s.dc) {
             HIPCHK(c, hipMemcpyAsync(Hraw, s.Hraw, hraw * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -673,12 +700,14 @@ struct Capture {
 void cycle_profile(const Solver &s, const GmresState *hs, size_t xup_idx, int last) {
     vtk_ctx *c = s.c;
     const double n8 = 8.0 * s.n;
-    const double xb = n8 * (last + 1) + 2 * n8;   // V[0..last] (or V_last and p_last), x in/out
+    // V[0..last] (or V_last and p_last), x in/out; compressed: 4 B per stored entry
+    const double xb = (s.cb ? 0.5 : 1.0) * n8 * (last + 1) + 2 * n8;
     if (xup_idx < c->prof_pending.size()) c->prof_pending[xup_idx].bytes = xb;
     if (hs->xup_tag >= 0) {
         // the x update ran in update pass xup_tag: account it as the "xupdate" class and
         // drop the host-enqueued k_xupdate (it returned at entry)
-        const int cu = prof_class(c, "dc_update"), cb = prof_class(c, "band_step"), cx = prof_class(c, "xupdate");
+        const int cu = prof_class(c, s.cb ? "cb_update" : "dc_update"), cb = prof_class(c, "band_step"),
+                  cx = prof_class(c, s.cb ? "cb_xupdate" : "xupdate");
         for (size_t i = 0; i < xup_idx && i < c->prof_pending.size(); ++i) {
             auto &p = c->prof_pending[i];
             if ((p.cls == cu || p.cls == cb) && p.col == hs->xup_tag) { p.cls = cx; p.col = -1; p.bytes = xb; }
@@ -689,7 +718,7 @@ void cycle_profile(const Solver &s, const GmresState *hs, size_t xup_idx, int la
 }
 
 // ||b||, ||M b|| (M b into V[0]) and x.any(); then the state record on the host (hs)
-int initial_norms(Solver &s, bool &r_is_b) {
+int initial_norms(Solver &s, bool &r_is_b, bool &basis_mixed) {
     vtk_ctx *c = s.c;
     vtk_prec *M = s.M;
     const int64_t n = s.n;
@@ -701,19 +730,27 @@ int initial_norms(Solver &s, bool &r_is_b) {
       HIPCHK(c, launch_dot(s.b, nullptr, n, s.part[0], s.G, c->stream)); }
     TRY(reduce(c, s.part[0], s.G, rb));
     HIPCHK(c, launch_finalize(rb, &ds->scal[0], 1, c->stream));
-    // M b goes to V[0]: with x0 = 0 it is the first cycle's psolve(r) (run_gmres)
+    // M b goes to V[0] (the cycle's start direction): with x0 = 0 it is the first cycle's psolve(r) (run_gmres)
     { Prof pf(c, prec_cls(M), -1, prec_row_bytes(M) * n + 2 * n8);
-      TRY(prec_apply(c, M, n, s.b, s.V, nullptr, s.part[1], nullptr, s.G, nullptr, 0, nullptr)); }
+      TRY(prec_apply(c, M, n, s.b, s.start(), nullptr, s.part[1], nullptr, s.G, nullptr, 0, nullptr)); }
     TRY(reduce(c, s.part[1], s.G, rmb));
     HIPCHK(c, launch_finalize(rmb, &ds->scal[1], 1, c->stream));
     // `r = b - matvec(x) if x.any() else b.copy()` (iterative.py:737): any nonzero x0 on any rank
     HIPCHK(c, hipMemsetAsync(&ds->scal[2], 0, sizeof(double), c->stream));
     { Prof pf(c, "any", -1, n8);
       HIPCHK(c, launch_any_nonzero(s.x, n, &ds->scal[2], c->stream)); }
-    if (c->dist) TRY(comm_allreduce(c, &ds->scal[2], 1));
-    double x_any = 0.0;
-    TRY(read_back(c, x_any, &ds->scal[2]));
-    r_is_b = x_any == 0.0;
+    // ... and, in the same all-reduce, the ranks' choice of basis storage: [3] the ranks that chose
+    // float32, [4] the ranks (every rank joins whatever it chose; basis_mixed: they disagree)
+    double flags[3] = {0.0, 0.0, 0.0};
+    if (c->dist) {
+        const double mine[2] = {c->basis == VTK_BASIS_F32 ? 1.0 : 0.0, 1.0};
+        HIPCHK(c, hipMemcpyAsync(&ds->scal[3], mine, sizeof(mine), hipMemcpyHostToDevice, c->stream));
+        TRY(comm_allreduce(c, &ds->scal[2], 3));
+    }
+    HIPCHK(c, hipMemcpyAsync(flags, &ds->scal[2], (c->dist ? 3 : 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r_is_b = flags[0] == 0.0;
+    basis_mixed = c->dist && flags[1] != 0.0 && flags[1] != flags[2];
     return VTK_OK;
 }
 
@@ -743,11 +780,16 @@ int run_cycle(Solver &s, const StepPlan &P, const Capture &cap, int64_t it, bool
     Red rv = rz;
     if (!r_ready) {
         { Prof pf(c, prec_cls(s.M), -1, P.b_inv + 2 * P.n8);
-          TRY(prec_apply(c, s.M, n, s.r, s.V, nullptr, s.part[0], nullptr, s.G, nullptr, 0, &s.vote)); }
+          TRY(prec_apply(c, s.M, n, s.r, s.start(), nullptr, s.part[0], nullptr, s.G, nullptr, 0, &s.vote)); }
         TRY(reduce(c, s.part[0], s.G, rv));
     }
-    { Prof pf(c, "scale0", -1, 2 * P.n8);
-      SOFT(launch_scale0(rv, s.V, n, s.S, m, ds, s.G, c->stream)); }
+    if (s.cb) {   // the direction read, v^_0 stored and written back widened
+        Prof pf(c, "cb_scale0", -1, 20.0 * n);
+        SOFT(launch_cb_scale0(rv, s.pc[0], s.Vc, n, s.S, m, ds, s.G, c->stream));
+    } else {
+        Prof pf(c, "scale0", -1, 2 * P.n8);
+        SOFT(launch_scale0(rv, s.V, n, s.S, m, ds, s.G, c->stream));
+    }
     *s.mirror = BIG_COL;
     // x as the cycle finds it: the x update may run inside an update pass of the cycle
     const bool cap_now = cap.on && (c->cap_cycle == -2 || c->cap_cycle == it);
@@ -759,8 +801,13 @@ int run_cycle(Solver &s, const StepPlan &P, const Capture &cap, int64_t it, bool
         TRY(mgs_cycle(s, P));
     }
     const size_t xup_idx = c->prof_pending.size();
-    { Prof pf(c, "xupdate", -1, 0.0);   // bytes set once the stop column is known
-      SOFT(launch_xupdate(s.H, s.S, s.V, s.ld, s.x, n, m, ds, s.G, c->stream)); }
+    if (s.cb) {
+        Prof pf(c, "cb_xupdate", -1, 0.0);
+        SOFT(launch_cb_xupdate(s.H, s.S, s.Vc, s.ld, s.x, n, m, ds, s.G, c->stream));
+    } else {
+        Prof pf(c, "xupdate", -1, 0.0);   // bytes set once the stop column is known
+        SOFT(launch_xupdate(s.H, s.S, s.V, s.ld, s.x, n, m, ds, s.G, c->stream));
+    }
     if (cap_now) TRY(cap.copy_cycle(s));
     TRY(residual(s, P, rz));
     // across ranks: the cycle's failure vote (a launch of some rank failed in this cycle; the
@@ -782,8 +829,10 @@ int run_cycle(Solver &s, const StepPlan &P, const Capture &cap, int64_t it, bool
     if (cap_now) cap.commit(s, hs, it, last);
     if (c->prof_on) cycle_profile(s, hs, xup_idx, last);
     const double bytes_spmv = P.b_csr + 16.0 * n, bytes_pc = P.b_inv + 16.0 * n;
-    for (int j = 0; j <= last; ++j) st.bytes_moved += bytes_spmv + bytes_pc + 8.0 * n * (2 * j + 8);
-    st.bytes_moved += bytes_spmv + 24.0 * n + bytes_pc + 24.0 * n + 8.0 * n * (last + 2);
+    // per step: operator, preconditioner, the two basis passes (float64 8(j+4) + 8(j+2) B per row and
+    // 16 B for the step's other vector traffic; compressed: 4j+28 + 4j+16); then the x update
+    for (int j = 0; j <= last; ++j) st.bytes_moved += bytes_spmv + bytes_pc + (s.cb ? (double)n * (8.0 * j + 60.0) : 8.0 * n * (2 * j + 8));
+    st.bytes_moved += bytes_spmv + 24.0 * n + bytes_pc + 24.0 * n + (s.cb ? (double)n * (4.0 * (last + 1) + 16.0) : 8.0 * n * (last + 2));
     st.restarts = it + 1;
     return VTK_OK;
 }
@@ -865,8 +914,15 @@ int vtk::run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double r
     s.vote = Vote{c, &c->d_scal[DC_VOTE + 1]};
     s.dc = c->orth == VTK_ORTH_DCGS2 || (c->orth == VTK_ORTH_AUTO && m <= DC_MAXJ);
     if (s.dc && m > DC_MAXJ) return fail(c, VTK_ERR_ARG, "DCGS2 supports restart <= 32 (use VTK_ORTH_MGS)");
+    // the compressed basis runs on the DCGS2 sequence only.  One rank refuses here; across ranks after
+    // the ranks have compared their choices (initial_norms), so that all of them leave together
+    const bool cb_mgs = c->basis == VTK_BASIS_F32 && !s.dc;
+    const char *cb_mgs_msg = "VTK_BASIS_F32 runs on the DCGS2 sequence only (restart <= 32 with VTK_ORTH_AUTO or VTK_ORTH_DCGS2); "
+                             "the MGS sequence keeps the float64 basis";
+    if (cb_mgs && !c->dist) return fail(c, VTK_ERR_ARG, cb_mgs_msg);
+    s.cb = c->basis == VTK_BASIS_F32 && s.dc;
     bool band_possible = false;
-    s.band = band_eligible(s, band_possible);
+    s.band = band_eligible(s, band_possible) && !s.cb;
     TRY(band_agree(s, band_possible));
     TRY(layout_workspace(s));
     Capture cap;
@@ -879,8 +935,10 @@ int vtk::run_gmres(vtk_csr *A, vtk_prec *M, const double *b, double *x, double r
     HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(GmresState), hipMemcpyHostToDevice, c->stream));
     if (c->dist) HIPCHK(c, hipMemsetAsync(&c->d_scal[DC_VOTE + 1], 0, sizeof(double), c->stream));   // no failure yet
     s.fail_pending = c->tune.fail_step >= 0;
-    bool r_is_b = true;
-    TRY(initial_norms(s, r_is_b));
+    bool r_is_b = true, basis_mixed = false;
+    TRY(initial_norms(s, r_is_b, basis_mixed));
+    if (basis_mixed) return fail(c, VTK_ERR_ARG, "vtk_gmres: the ranks disagree on the basis storage (vtk_gmres_set_basis): set the same on every rank");
+    if (cb_mgs) return fail(c, VTK_ERR_ARG, cb_mgs_msg);
     Red rz{c->d_part + 5 * GMAX, spmv_grid(spmv_in(A, P.rtiles, x))};
     if (r_is_b) {
         // r = b: ||r|| = ||b||, and psolve(r) = M b is already in V[0] with its partials

@@ -289,6 +289,8 @@ struct vtk_ctx {
     bool comm_broken = false;             // an RCCL call failed: vtk_ctx_destroy aborts the communicator
     vtk_host_comm hops{};
     int orth = VTK_ORTH_AUTO;
+    int basis = VTK_BASIS_F64;            // vtk_gmres_set_basis: the Krylov basis' storage
+    vtk_basis_info basis_info{};          // ... and what the last vtk_gmres used (vtk_gmres_basis_info)
     vtk::Tuning tune;                     // A/B switches (vtk_ctx_set_tuning), env at creation
     int n_cu = 0;                         // compute units (band step grid)
     // scratch shared by calls on this context
@@ -624,15 +626,35 @@ hipError_t launch_spmv_dc(const SpmvIn &in, double *w, const BjOp &bj, const dou
 hipError_t launch_dc_finalize(const double *part, int cnt, int j, int with_w, double *scal,
                               const int *stop_col, int col, hipStream_t s);
 // part != null: reduce the G partials in-kernel (one GPU); else read the all-reduced scal
+// r_meas: step 0 measures ||v_0|| = sqrt(alpha) instead of taking 1 (the compressed basis)
 hipError_t launch_dc_scalar(const double *part, int cnt, const double *scal, int j, int m,
                             int closing, double *Hraw, double *H, double *S, double *giv,
-                            DcCoef *cf, GmresState *st, int *stop_map, hipStream_t s);
+                            DcCoef *cf, GmresState *st, int *stop_map, hipStream_t s, int r_meas = 0);
 // update pass of step j; when the step's scalar kernel stopped the cycle (st->xup_tag == j) it
 // does the cycle's x update instead: x += V[0..c] y, y = H^-1 S at c = stop_col (j-1 or j; for
 // c = j the v_j of the pass is formed in registers), reading the basis once
 hipError_t launch_dc_update(double *V, int64_t ld, int j, const double *w, int64_t n,
                             const DcCoef *cf, int grid, const GmresState *st, double *x,
                             const double *H, const double *S, int m, int nt_pw, hipStream_t s);
+
+// Compressed basis (vtk_gmres_set_basis VTK_BASIS_F32; vtk_cbasis.hip): the split DCGS2
+// step's passes with the finalised columns in Vc[(m + 1) x ld] floats and the candidates p_j, p_{j+1} in
+// two float64 vectors.  Partials, stop test, coefficients and the x update's rule as the float64
+// launches above; every pointer 16-byte aligned, ld a multiple of 4 (hipErrorInvalidValue otherwise).
+// launch_cb_scale0: p0 = p0 / sqrt(reduce(p)), Vc[0] = (float) p0, p0 = (double) Vc[0]
+hipError_t launch_cb_scale0(Red p, double *p0, float *Vc, int64_t n, double *S, int m, GmresState *st, int grid,
+                            hipStream_t s);
+hipError_t launch_cb_dots(const float *Vc, int64_t ld, int j, const double *p, const double *w, int64_t n,
+                          double *part, int grid, const int *stop_col, int col, hipStream_t s);
+// reads p_j (pj) and w, stores Vc[j] (j >= 1) and p_{j+1} (pn != pj); st->xup_tag == j: the x update
+hipError_t launch_cb_update(float *Vc, int64_t ld, int j, const double *pj, const double *w, double *pn, int64_t n,
+                            const DcCoef *cf, int grid, const GmresState *st, double *x, const double *H,
+                            const double *S, int m, hipStream_t s);
+hipError_t launch_cb_xupdate(const double *H, const double *S, const float *Vc, int64_t ld, double *x, int64_t n,
+                             int m, const GmresState *st, int grid, hipStream_t s);
+// the capture hook's V: the m + 1 columns widened, the open candidate (pa / pb by parity) in its column
+hipError_t launch_cb_capture(const float *Vc, int64_t ld, int m, const double *pa, const double *pb,
+                             const GmresState *st, double *out, hipStream_t s);
 
 // Variant bits of the band step (Tuning::band_opt -> StepPlan::band_opt -> BandK::opt), for the
 // canonical-row kernels (VMODE 2) only: step_plan masks them off elsewhere.  Compile-time bits pick

@@ -2663,16 +2663,16 @@ hipError_t launch_dc_finalize(const double *part, int cnt, int j, int with_w, do
 __global__ __launch_bounds__(1024) void k_dc_scalar(const double *part, int cnt, const double *scal, int j,
                                                     int m, int closing, double *Hraw, double *H,
                                                     double *S, double *giv, DcCoef *cf,
-                                                    GmresState *st, int *stop_map) {
+                                                    GmresState *st, int *stop_map, int r_meas) {
     __shared__ DcScalarLds sl;
-    dc_scalar_body<false, 3>(sl, part, cnt, scal, j, m, closing, Hraw, H, S, giv, cf, st, stop_map);
+    dc_scalar_body<false, 3>(sl, part, cnt, scal, j, m, closing, Hraw, H, S, giv, cf, st, stop_map, ScalarNoTrace{}, r_meas != 0);
 }
 
 hipError_t launch_dc_scalar(const double *part, int cnt, const double *scal, int j, int m, int closing,
                             double *Hraw, double *H, double *S, double *giv, DcCoef *cf, GmresState *st,
-                            int *stop_map, hipStream_t s) {
+                            int *stop_map, hipStream_t s, int r_meas) {
     hipLaunchKernelGGL(k_dc_scalar, dim3(1), dim3(1024), 0, s, part, cnt, scal, j, m, closing, Hraw, H, S, giv,
-                       cf, st, stop_map);
+                       cf, st, stop_map, r_meas);
     return hipGetLastError();
 }
 

@@ -114,7 +114,7 @@ template <bool SC1, int QW, class TR = ScalarNoTrace>
 __device__ __forceinline__ void dc_scalar_body(DcScalarLds &sl, const double *part, int cnt, const double *scal,
                                                int j, int m, int closing, double *Hraw, double *H, double *S,
                                                double *giv, DcCoef *cf, GmresState *st, int *stop_map,
-                                               TR tr = TR{}) {
+                                               TR tr = TR{}, bool r_meas = false) {
     double *const q = sl.q, *const hr_s = sl.hr_s, *const giv_s = sl.giv_s, *const S_s = sl.S_s;
     double *const hc_s = sl.hc_s, *const hj = sl.hj, *const e_s = sl.e_s, *const sc = sl.sc;
     int *const flags = sl.flags;
@@ -215,8 +215,10 @@ __device__ __forceinline__ void dc_scalar_body(DcScalarLds &sl, const double *pa
     if (wv == 0) {
         const double svk = lane < j ? sv[lane] : 0.0, zvk = lane < j ? zv[lane] : 0.0;
         const double ss = wave_allsum(svk * svk), sz = wave_allsum(svk * zvk);
+        // step 0 takes ||v_0|| = 1 from the cycle start; r_meas (the compressed basis, whose stored
+        // v^_0 is a float32 rounding of a unit vector) measures it like every later step: r = sqrt(alpha)
         double r = 1.0;
-        if (j >= 1) {
+        if (j >= 1 || r_meas) {
             const double r2 = alpha - ss;
             r = __builtin_sqrt(r2 > 0.0 ? r2 : alpha);
         }

@@ -34,7 +34,7 @@ __all__ = ["Context", "default_context", "csr_matrix", "load_npz", "save_npz", "
            "vlasov_line_period",
            "vlasov_line_directions",
            "vlasov_line_stride", "bicgstab", "BicgstabStats", "last_bicgstab_stats",
-           "ArnoldiCapture", "last_arnoldi"]
+           "ArnoldiCapture", "last_arnoldi", "BasisInfo", "last_basis_info"]
 
 VlasovParams = _abi.VlasovParams
 
@@ -155,6 +155,20 @@ class Context:
     def set_orth(self, orth: int):
         check(lib().vtk_gmres_set_orth(self._h, int(orth)), self._h)
         self.orth = int(orth)
+
+    basis = _abi.BASIS_F64
+
+    def set_basis(self, basis: int):
+        """Storage of the Krylov basis in :func:`gmres` (``vtk_gmres_set_basis``):
+        ``_abi.BASIS_F64`` (default) or ``_abi.BASIS_F32``, the compressed basis."""
+        check(lib().vtk_gmres_set_basis(self._h, int(basis)), self._h)
+        self.basis = int(basis)
+
+    def basis_info(self) -> "BasisInfo":
+        o = _abi.BasisInfo()
+        check(lib().vtk_gmres_basis_info(self._h, C.byref(o)), self._h)
+        return BasisInfo(requested=int(o.requested), used=int(o.used), basis_bytes=int(o.basis_bytes),
+                         workspace_bytes=int(o.workspace_bytes))
 
     def set_tuning(self, key: str, value: int):
         """A/B and test switch of this context (``vtk_ctx_set_tuning``; keys in
@@ -938,6 +952,24 @@ def last_stats() -> SolveStats | None:
 
 
 @dataclass
+class BasisInfo:
+    """``vtk_basis_info``: the basis storage set on the context, and what the last :func:`gmres`
+    on it used (0 float64, 1 float32) with that solve's basis and workspace bytes."""
+    requested: int
+    used: int
+    basis_bytes: int
+    workspace_bytes: int
+
+
+_last_basis_ctx = None
+
+
+def last_basis_info() -> BasisInfo | None:
+    """:class:`BasisInfo` of the last :func:`gmres` call (None before the first)."""
+    return None if _last_basis_ctx is None else _last_basis_ctx.basis_info()
+
+
+@dataclass
 class ArnoldiCapture:
     """One captured restart cycle (``vtk_gmres_captured``; include/vtkrylov.h states which columns
     of ``V`` are final).  ``V``: (restart + 1, n_local), row k = column k of the basis.  ``H``:
@@ -989,7 +1021,7 @@ def last_arnoldi(ctx: Context | None = None) -> ArnoldiCapture:
 
 
 def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=None,
-          callback=None, callback_type=None, orth=None):
+          callback=None, callback_type=None, orth=None, basis=None):
     """``scipy.sparse.linalg.gmres`` on the GPU (iterative.py:582-841, left-preconditioned
     restarted GMRES: SciPy's control flow, ptol schedule, ``dlartg`` Givens rotations and
     ``info`` convention).  Returns ``(x, info)``.
@@ -1001,13 +1033,22 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     iteration count may differ by one.  ``orth="mgs"`` runs SciPy's exact
     modified Gram-Schmidt sequence (iterative.py:755-759); ``orth="dcgs2"`` forces DCGS2.
 
+    Basis storage: ``basis=None`` keeps the context's setting (float64 unless
+    :meth:`Context.set_basis` changed it); ``basis="float32"`` stores the orthonormal columns in
+    float32 and computes in float64 (compressed-basis GMRES, DESIGN.md §3p: about two thirds of
+    the workspace, DCGS2 only, no line-band step; results agree with the float64 basis to the
+    tolerance, not bit for bit); ``basis="float64"`` forces the full basis.  Any other value
+    raises ValueError.  :func:`last_basis_info` reports what the solve used.
+
     ``A``: a :class:`CsrOperator` or any SciPy sparse matrix (uploaded).  ``M``: None, a
     :class:`BlockJacobi`, a :class:`LineJacobi`, a :class:`LineProduct`, a :class:`LineCyclic` or a :class:`Neumann` wrapper built on ``A``; any other preconditioner raises TypeError (no CPU
     fallback).  ``callback`` is not supported (the Arnoldi loop never returns to the host).
     ``restart``/``maxiter``: None = SciPy's defaults (20 / 10 n); explicit values must be
     positive integers (ValueError otherwise).
     """
-    global _last_stats
+    global _last_stats, _last_basis_ctx
+    if basis is not None and (not isinstance(basis, str) or basis not in _abi.BASIS):
+        raise ValueError(f"vtkrylov.gmres: basis must be None, 'float64' or 'float32', got {basis!r}")
     if callback is not None:
         raise NotImplementedError("vtkrylov.gmres: callbacks would force a host round trip per "
                                   "Arnoldi step and are not supported")
@@ -1042,6 +1083,11 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     if orth is not None:
         prev = A.ctx.orth
         A.ctx.set_orth(_abi.ORTH[orth])
+    prev_basis = None
+    if basis is not None:
+        prev_basis = A.ctx.basis
+        A.ctx.set_basis(_abi.BASIS[basis])
+    _last_basis_ctx = A.ctx
     try:
         check(lib().vtk_gmres(A.handle, None if M is None else M.handle, vb.ptr, vx.ptr,
                               float(rtol), float(atol), 0 if restart is None else int(restart),
@@ -1050,6 +1096,8 @@ def gmres(A, b, x0=None, *, rtol=1e-5, atol=0., restart=None, maxiter=None, M=No
     finally:
         if prev is not None:
             A.ctx.set_orth(prev)
+        if prev_basis is not None:
+            A.ctx.set_basis(prev_basis)
     _last_stats = SolveStats(**st.as_dict())
     return x, info.value
 

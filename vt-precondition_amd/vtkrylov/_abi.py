@@ -32,6 +32,10 @@ ORTH_DCGS2 = 1
 ORTH_AUTO = 2
 ORTH = {"mgs": 0, "dcgs2": 1, "auto": 2}
 
+BASIS_F64 = 0
+BASIS_F32 = 1
+BASIS = {"float64": 0, "float32": 1}   # vtk_basis (vtk_gmres_set_basis)
+
 
 class VlasovParams(C.Structure):
     _fields_ = [("dim", C.c_int), ("fp32", C.c_int), ("shape", C.c_int64 * 4),
@@ -132,6 +136,8 @@ PROTOTYPES = {
                                C.POINTER(C.c_int), C.POINTER(BicgstabStats)]),
     "vtk_gmres_set_orth": (C.c_int, [P, C.c_int]),
     "vtk_gmres_set_band": (C.c_int, [P, C.c_int]),
+    "vtk_gmres_set_basis": (C.c_int, [P, C.c_int]),
+    "vtk_gmres_basis_info": (C.c_int, [P, C.c_void_p]),
     "vtk_gmres_capture": (C.c_int, [P, C.c_int]),
     "vtk_gmres_captured": (C.c_int, [P, C.c_void_p]),
     "vtk_gmres_captured_read": (C.c_int, [P, C.c_int, P, C.c_int]),
@@ -148,6 +154,11 @@ class ArnoldiInfo(C.Structure):
     _fields_ = [("n_local", C.c_int64), ("ld", C.c_int64), ("restart", C.c_int), ("cycle", C.c_int),
                 ("cols", C.c_int), ("final_cols", C.c_int), ("orth", C.c_int), ("band", C.c_int),
                 ("has_hraw", C.c_int), ("stop_col", C.c_int), ("breakdown", C.c_int), ("xup_tag", C.c_int)]
+
+
+class BasisInfo(C.Structure):   # vtk_basis_info
+    _fields_ = [("requested", C.c_int32), ("used", C.c_int32), ("basis_bytes", C.c_int64),
+                ("workspace_bytes", C.c_int64)]
 
 
 # vtk_gmres_captured_read items

@@ -89,6 +89,9 @@ class SolverConfig:
     # preconditioner/neumann_degree (optional node; absent: 1, the preconditioner itself): the type
     # above wrapped in vtkrylov.neumann of this degree, 1..8
     neumann_degree: int = 1
+    # solver/basis (optional node; absent: float64): float32 = the compressed Krylov basis of
+    # vtkrylov.gmres(..., basis="float32") (gmres with DCGS2 only)
+    basis: str = "float64"
 
     @classmethod
     def load(cls, path: str = DEFAULT_XML, **overrides) -> "SolverConfig":
@@ -123,6 +126,7 @@ class SolverConfig:
         cfg.line_period = int(t.get_optional("preconditioner/line_period", "0") or 0)
         cfg.line_span = int(t.get_optional("preconditioner/line_span", "0") or 0)
         cfg.neumann_degree = int(t.get_optional("preconditioner/neumann_degree", "1") or 1)
+        cfg.basis = (t.get_optional("solver/basis", "float64") or "float64").lower()
         for k, v in overrides.items():
             if v is not None:
                 setattr(cfg, k, v)
@@ -140,6 +144,10 @@ class SolverConfig:
             raise ValueError("preconditioner/line_span: cyclic lines that span the ranks are no base of the Neumann wrapper")
         if cfg.orth not in ("auto", "mgs", "dcgs2"):
             raise ValueError(f"unknown orthogonalisation {cfg.orth!r}")
+        if cfg.basis not in ("float64", "float32"):
+            raise ValueError(f"unknown solver/basis {cfg.basis!r} (float64, float32)")
+        if cfg.basis == "float32" and (cfg.method != "gmres" or cfg.orth == "mgs"):
+            raise ValueError("solver/basis float32 belongs to gmres with the DCGS2 sequence (solver/orth auto or dcgs2)")
         if cfg.method not in ("gmres", "bicgstab"):
             raise ValueError(f"unknown solver/method {cfg.method!r} (gmres, bicgstab)")
         if cfg.gpus < 1:

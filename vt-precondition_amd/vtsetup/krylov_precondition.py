@@ -152,12 +152,12 @@ class KrylovPrecondition:
                                     "t_solve_s": st.t_solve}
             return
         self.x, info = vk.gmres(self.A, self.b, rtol=c.rtol, atol=c.atol, restart=c.restart,
-                                maxiter=c.maxiter or None, M=self.M, orth=c.orth)
+                                maxiter=c.maxiter or None, M=self.M, orth=c.orth, basis=c.basis)
         st = vk.last_stats()
         t_solve = self._max(st.t_solve)
         self.result["solve"] = {"info": info, "inner_iters": st.inner_iters,
                                 "restarts": st.restarts, "rnorm": st.rnorm, "bnorm": st.bnorm,
-                                "t_solve_s": t_solve, "band_step": bool(st.band),
+                                "t_solve_s": t_solve, "band_step": bool(st.band), "basis": c.basis,
                                 "iters_per_s": st.inner_iters / t_solve if t_solve else None}
 
     def gather_x(self):
@@ -300,6 +300,8 @@ def test_main(argv=None) -> int:
     ap.add_argument("--line-span", action="store_const", const=1, default=None,
                     help="line_cyclic: the lines may span the ranks (overrides preconditioner/line_span)")
     ap.add_argument("--orth", choices=["auto", "mgs", "dcgs2"])
+    ap.add_argument("--basis", choices=["float64", "float32"],
+                    help="storage of the Krylov basis (overrides solver/basis; float32: the compressed basis)")
     ap.add_argument("--method", choices=["gmres", "bicgstab"], help="solver (overrides solver/method)")
     ap.add_argument("--gpus", type=int, help="ranks (overrides run/gpus)")
     ap.add_argument("--comm", choices=["rccl", "host"], help="transport (overrides run/comm)")
@@ -309,7 +311,7 @@ def test_main(argv=None) -> int:
     try:
         cfg = SolverConfig.load(a.xml, config=a.config, report=a.report, operator_file=a.operator_file,
                                 preconditioner=a.preconditioner, orth=a.orth, gpus=a.gpus, comm=a.comm, method=a.method,
-                                line_span=a.line_span)
+                                line_span=a.line_span, basis=a.basis)
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
             return _rank_main(cfg, a)
         if cfg.gpus > 1:
